@@ -23,9 +23,9 @@ reports what actually ran.
 
 Prints ONE JSON line (rank 0), kept under 6 KB so that the tail of a driver's log holds all of it.  `value` = per-sample
 grad+prox updates of the SWEEP per second over all ranks (one update = one row's gradient into the aggregate + its share of the
-fused prox), inputs resident in HBM before the timed region; `epochs_per_sec` = sweeps per second.  The other three kinds of
-update SURVEY.md section 8d defines are reported at top level of the same line, measured after the timed region on rank 0, each
-as {value, roofline{...frac}, cpu_baseline{...}}:
+fused prox), inputs resident in HBM before the timed region; `epochs_per_sec` = sweeps per second.  With --full, the other three
+kinds of update SURVEY.md section 8d defines are reported at top level of the same line, measured after the timed region on rank 0,
+each as {value, roofline{...frac}, cpu_baseline{...}}:
     svrg_updates_per_sec       one step of the SVRG inner cycle (S3), from ONE real outer iteration m = N at the metric's size
     svrg_epochs_per_sec_N10M   that outer iteration as a whole (m = N updates + tail + full-gradient sweep)
     saga_updates_per_sec       one SAGA step (G3) at BASELINE config #3 (N x 1024 fp32 + the N x 1024 table), and in fp64
@@ -35,6 +35,15 @@ as {value, roofline{...frac}, cpu_baseline{...}}:
 `cpu_baseline` is the single-threaded CPU oracle on a bounded sample of the same rows (also with --gpus N > 1: rank 0 times it
 after the timed region while the other ranks wait at the final barrier).  The secondary timings (`extra`) go to a side file
 (gpurun_out/bench_extras.json when that directory exists, else bench_extras.json beside this script) and to stderr.
+
+A plain run (no --full) does only what the headline needs: set-up, warm-up, the timed steps (with the HIP-event `roofline` of
+the same steps), --dump-outputs if given, the line.  --full adds, after the timed region, everything else: `cpu_baseline`, the
+update figures above, `full_pass_K_solves`, the collective timed alone (several ranks) and the secondary timings; --no-cpu,
+--no-chains and --no-extras leave parts of that out again.
+
+--dump-outputs DIR writes what the last timed step handed its caller, on rank 0: `x.npy` (the iterate x+ after the prox) and
+`av.npy` (the full gradient it was computed from), d values each in the run's dtype.  The inputs are generated from fixed seeds,
+so two builds run with the same arguments can be compared output for output.
 
 Before a rank allocates its 82 GB, `collective_preflight` sends 1 KB through every collective path that is going to be used
 (torch.distributed, the library's own ncclAllReduce, the peer mailboxes when asked for), each stage under a watchdog: a path that
@@ -79,7 +88,15 @@ def parse(argv=None):
     ap.add_argument("--preflight-seconds", type=float, default=120.0, help="watchdog of each collective preflight stage")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU work at all: rendezvous, barrier and the JSON relay only (CPU test of the launcher)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the CPU baselines, the SVRG / SAGA / Finito update figures, the "
+                         "collective alone and the secondary timings (a plain run times the sweep only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (x.npy, av.npy) to DIR")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ======================================================================================================================
@@ -437,9 +454,16 @@ def run_rank(args):
     ctx.synchronize()
     kernel_name = ctx.last_kernel()
 
+    # ---- what the last timed step handed its caller: the iterate it wrote and the full gradient it used ---------------------
+    if args.dump_outputs and rank == 0:
+        last = args.warmup + args.steps - 1
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in (("x", xb if last % 2 == 0 else xa), ("av", av)):
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), t.cpu().numpy())
+
     # ---- the collective alone: K all-reduces of d+1 scalars back to back on the compute stream ---------------------------
     allreduce_us, allreduce_peer_us = None, None
-    if world > 1 or force_dist:
+    if args.full and (world > 1 or force_dist):
         buf = torch.zeros(d + 1, dtype=tdt, device=dev)
         reps = 200
         try:
@@ -513,7 +537,7 @@ def run_rank(args):
         "metric": METRIC,
         "metric_definition": "the SVRG full-gradient + prox sweep (SVRG_basic.jl:87-92): one update = one row's gradient into the aggregate "
                              "+ its share of the fused prox; value = N_total * steps / time.  The dependent-chain updates of SURVEY 8d "
-                             "are the *_per_sec entries below.",
+                             "are the *_per_sec entries below (with --full).",
         "value": value,
         "unit": UNIT,
         "n_gpus": world,
@@ -545,7 +569,7 @@ def run_rank(args):
 
     # ---- everything below runs on rank 0 only, after the timed region; with several ranks the others wait at the final barrier ----
     # cpu_baseline: the single-threaded oracle (reference-shaped sequential pass) on a bounded sample of this rank's rows
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         try:
             from oracle import oracle as O
             n_s = min(args.cpu_rows, n_local)
@@ -573,7 +597,7 @@ def run_rank(args):
 
     # the updates SURVEY.md 8d defines: the sequential SVRG / SAGA chains and the Finito batch, at the configs' own sizes
     args.cpu_sweep_rate = (out.get("cpu_baseline") or {}).get("value")
-    if rank == 0 and not args.no_chains:
+    if rank == 0 and args.full and not args.no_chains:
         cctx = ctx
         try:
             if world > 1 or force_dist:
@@ -591,7 +615,7 @@ def run_rank(args):
             if cctx is not ctx:
                 cctx.close()
 
-    if not args.no_extras and world == 1 and rank == 0:
+    if args.full and not args.no_extras and world == 1 and rank == 0:
         ex_dir = os.path.join(ROOT, "gpurun_out") if os.path.isdir(os.path.join(ROOT, "gpurun_out")) else ROOT
         ex_path = os.path.join(ex_dir, "bench_extras.json")
         try:

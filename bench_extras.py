@@ -1,4 +1,4 @@
-"""Secondary measurements reported under "extra" by `bench.py --extras` (and by tools/): the sequential chains
+"""Secondary measurements reported under "extra" by `bench.py --full` (and by tools/): the sequential chains
 (SURVEY.md section 8a rows S3, G3, F3 with r = 1) and the batch-parallel table kernels (G2, F2, F3).  These are reported
 honestly against the HBM bound although the chains are latency-bound by construction (one dependent step at a time).
 """

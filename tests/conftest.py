@@ -2,6 +2,10 @@ import os
 import sys
 
 import pytest
+# torch before any test can dlopen libciao_hip.so: torch's bundled HIP runtime carries the same soname as ROCm's, so a library
+# loaded after torch shares it.  Loaded before torch (the CPU tests do), the library would bring ROCm's own HIP runtime into the
+# process beside torch's, and in a session that runs CPU and GPU tests together the library would find no device.
+import torch  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:

@@ -96,7 +96,8 @@ def test_parent_never_imports_torch():
 def test_two_ranks_on_the_one_gpu_real_step():
     """The real sweep, two ranks sharing GPU 0 (RCCL takes one rank per device, so the rehearsal collective is gloo): the
     line must say n_gpus = 2, count both shards' rows, and name the collective that actually ran."""
-    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--rows-per-gpu", "200000", "--no-cpu", "--no-extras", "--no-chains"],
+    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--rows-per-gpu", "200000", "--full", "--no-cpu", "--no-extras",
+              "--no-chains"],
              {"CIAO_BENCH_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-3000:]
     j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -114,7 +115,7 @@ def test_two_ranks_on_the_one_gpu_real_step():
 def test_two_ranks_rank0_reports_cpu_baseline_and_the_update_figures():
     """With --gpus N > 1 rank 0 still times the CPU baseline and the chain / Finito figures (on its own shard, on a context without a
     collective) after the timed region, while the other rank waits at the final barrier."""
-    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--rows-per-gpu", "200000", "--no-extras", "--cpu-rows", "20000",
+    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--rows-per-gpu", "200000", "--full", "--no-extras", "--cpu-rows", "20000",
               "--cpu-seconds", "0.5", "--cpu-chain-seconds", "0.5", "--cpu-chain-updates", "2000", "--chain-rows", "100000"],
              {"CIAO_BENCH_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-3000:]
@@ -133,7 +134,8 @@ def test_two_ranks_rank0_reports_cpu_baseline_and_the_update_figures():
 def test_two_ranks_on_the_one_gpu_real_step_through_the_peer_mailboxes():
     """CIAO_BENCH_COLLECTIVE=peer: the sweep's reductions travel through the peer mailboxes (csrc/peer_kernels.h), fused into
     finalize / epilogue; the line names that collective and reports its per-step cost."""
-    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--rows-per-gpu", "200000", "--no-cpu", "--no-extras", "--no-chains"],
+    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--rows-per-gpu", "200000", "--full", "--no-cpu", "--no-extras",
+              "--no-chains"],
              {"CIAO_BENCH_BACKEND": "gloo", "CIAO_BENCH_COLLECTIVE": "peer"})
     assert r.returncode == 0, r.stderr[-3000:]
     j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -14,8 +14,10 @@ export TMPDIR=/tmp
 for part in "${@:-a}"; do
 case "$part" in
 a)
-  echo "== bench (default)"; timeout -k 10 1000 python bench.py > "$O/bench_f64.json" 2> "$O/bench_f64.err"; echo "rc=$?"; python -c "
-import json;j=json.load(open('$O/bench_f64.json'));print(j['value'], j['ms_per_step'], j['roofline']['frac'], j['roofline']['kernel_avg_ms']); print(j['svrg_updates_per_sec']['value'], j['saga_updates_per_sec']['value'], j['finito_samples_per_sec']['value']); print(j['cpu_baseline']['value'], j.get('extras_file'))"; cp -f "$R/gpurun_out/bench_extras.json" "$O/bench_extras.json" 2>/dev/null
+  echo "== bench (default)"; timeout -k 10 1000 python bench.py --full > "$O/bench_f64.json" 2> "$O/bench_f64.err"; echo "rc=$?"; python -c "
+import json;j=json.load(open('$O/bench_f64.json'));print(j['value'], j['ms_per_step'], j['roofline']['frac'], j['roofline']['kernel_avg_ms']); print(j['svrg_updates_per_sec']['value'], j['saga_updates_per_sec']['value'], j['finito_samples_per_sec']['value']); print(j['cpu_baseline']['value'], j.get('extras_file'))
+import os, shutil; x = os.path.join('$R', j.get('extras_file', ''))
+if os.path.isfile(x): shutil.copy(x, '$O/bench_extras.json')"
   echo "== bench f32"; timeout -k 10 600 python bench.py --dtype f32 --no-extras --no-chains > "$O/bench_f32.json" 2> "$O/bench_f32.err"; echo "rc=$?"; python -c "
 import json;j=json.load(open('$O/bench_f32.json'));print(j['value'], j['ms_per_step'], j['roofline']['frac'])"
   ;;
@@ -32,7 +34,7 @@ b)
   python tools/pmc_sweep_traffic.py ls_f64_N10000000_d1024 "$F64F" "$F64W" > "$O/pmc_traffic_1.json" && python tools/pmc_sweep_traffic.py ls_f32_N10000000_d1024 "$F32F" "$F32W" "$O/pmc_traffic_1.json" > "$O/pmc_traffic.json"; cat "$O/pmc_traffic.json"
   ;;
 c)
-  echo "== rocprof stats chains at N=10M"; (cd /tmp && timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_chains" -o c -- python3 "$R/bench.py" --steps 2 --warmup 1 --no-cpu --no-extras > "$O/prof_chains.log" 2>&1); echo "rc=$?"
+  echo "== rocprof stats chains at N=10M"; (cd "$TMPDIR" && timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_chains" -o c -- python3 "$R/bench.py" --steps 2 --warmup 1 --full --no-cpu --no-extras > "$O/prof_chains.log" 2>&1); echo "rc=$?"
   echo "== rocprof stats extras"; (cd /tmp && timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_extras" -o e -- python3 "$R/tools/run_extras.py" > "$O/extras.json" 2> "$O/extras.err"); echo "rc=$?"
   ;;
 esac
