@@ -82,6 +82,7 @@ SIGNATURES = {
     "ciao_full_gradient": (_i32, [_vp, _PP, _vp, _vp]),
     "ciao_proxgrad_step": (_i32, [_vp, _PP, _GP, _f64, _vp, _vp, _vp]),
     "ciao_objective": (_i32, [_vp, _PP, _GP, _vp, C.POINTER(_f64)]),
+    "ciao_certificate": (_i32, [_vp, _PP, _GP, _vp, _vp, _f64, C.POINTER(_f64)]),
     "ciao_svrg_init": (_i32, [_vp, _PP, _vp, _vp, _vp, _vp, _vp]),
     "ciao_svrg_inner": (_i32, [_vp, _PP, _GP, _f64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "ciao_svrg_iterate": (_i32, [_vp, _PP, _GP, _f64, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),

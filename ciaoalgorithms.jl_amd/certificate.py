@@ -1,0 +1,85 @@
+"""Optimality certificate and solve-to-tolerance: how far is a solver's iterate from the optimum?
+
+Every solver here runs exactly `maxit` iterations; `state.objective` tells the value reached, not its distance from the minimum.
+`Context.certificate` (include/ciao_hip.h: ciao_certificate) answers with two numbers computed on the device in one pass over A and
+one reduction over the d coordinates:
+
+    residual = || x - prox_{gamma g}(x - gamma grad f(x)) || / gamma     zero exactly at a minimiser, for every loss and prox here
+    gap      = F(x) + g(x) - D(theta)                                    lasso only: objective(x) - min <= gap for ANY x (weak duality)
+
+The gap exists for LeastSquares rows with g = NormL1(mu), mu > 0: the dual point theta = s (lam/N)(Ax - b),
+s = min(1, mu / ||grad f(x)||_inf), is feasible by construction and b'r = x'A'r - ||r||^2 removes every per-row quantity, so that
+D = F (2s - s^2) - s x.grad f(x) needs only the numbers the d-vector reduction leaves.  For the logistic loss the dual value needs
+the per-sample terms (an entropy of every margin): no gap there, `gap` is nan and `residual` is the certificate.
+
+    cert = Certificate(ctx, F, g, N, gamma)
+    x, it = SVRG(...)(x0, F=F, g=g, N=N, stop=stop_when(cert, gap=1e-8), check_every=k)
+
+`solvers.py` does not import this module: `stop_when` returns a plain callable for the functors' existing `stop=` keyword.
+"""
+from __future__ import annotations
+
+import math
+from typing import NamedTuple
+
+
+class CertificateResult(NamedTuple):
+    F: float               # (1/N) sum_i f_i(x)
+    g: float               # g(x): NormL1's value, 0 for Zero / a feasible Box point, +inf for an infeasible one
+    objective: float       # F + g
+    residual: float        # || x - prox_{gamma g}(x - gamma grad f(x)) ||_2 / gamma
+    grad_inf: float        # || grad f(x) ||_inf
+    x_dot_grad: float      # x . grad f(x)
+    box_violation: float   # max_k max(lo_k - x_k, x_k - hi_k, 0)
+    gap: float             # lasso duality gap (nan where it does not apply)
+
+
+def assemble(F, g_value, residual, grad_inf, x_dot_grad, box_violation, mu=None) -> CertificateResult:
+    """The named result from the six numbers of ciao_certificate, in double.  mu: NormL1's weight when the rows are LeastSquares
+    (the gap applies), else None."""
+    g = math.inf if box_violation > 0 else g_value
+    gap = math.nan
+    if mu is not None and mu > 0:
+        s = 1.0 if grad_inf == 0 else min(1.0, mu / grad_inf)
+        dual = F * (2 * s - s * s) - s * x_dot_grad
+        gap = F + g - dual
+    return CertificateResult(F, g, F + g, residual, grad_inf, x_dot_grad, box_violation, gap)
+
+
+class Certificate:
+    """cert(state) -> CertificateResult at solution(state).
+
+    F, g, N: what the solver call takes (operator objects, or device.PackedF / device.ProxG); gamma: the prox-gradient step of the
+    residual (any gamma > 0 certifies; 1 / L_max is the natural scale).  On a device state whose F came as operator objects the
+    iterable's own packing of them is used (no second copy of A on the device); a host-route state (backend == "host") is answered
+    in numpy by host_route.host_certificate.  ctx=None: the state's context."""
+
+    def __init__(self, ctx, F, g, N, gamma):
+        if not (gamma > 0 and math.isfinite(gamma)):
+            raise ValueError("gamma must be > 0 and finite")
+        self.ctx, self.F, self.g, self.N, self.gamma = ctx, F, g, int(N), float(gamma)
+
+    def __call__(self, state) -> CertificateResult:
+        from .solvers import solution
+        x = solution(state)
+        if getattr(state, "backend", None) == "host":
+            from . import host_route as HR
+            return HR.host_certificate(self.F, self.g, x, self.gamma, self.N)
+        from .device import PackedF
+        it = state._it
+        F, g = (self.F, self.g) if isinstance(self.F, PackedF) else (it.F, it.g)
+        return (self.ctx if self.ctx is not None else it.ctx).certificate(F, g, x, self.gamma)
+
+
+def stop_when(cert, gap=None, residual=None):
+    """A callable for the functors' `stop=` keyword: true at the first checked state whose certificate meets EVERY bound given
+    (gap <= gap, residual <= residual).  The last certificate is kept in `.last`."""
+    if gap is None and residual is None:
+        raise ValueError("give a bound: gap=, residual= or both")
+
+    def stop(state):
+        c = stop.last = cert(state)
+        return (gap is None or c.gap <= gap) and (residual is None or c.residual <= residual)
+
+    stop.last = None
+    return stop

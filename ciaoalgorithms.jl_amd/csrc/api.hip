@@ -5,6 +5,7 @@
 // Nothing here computes on the CPU: if the HIP runtime or the device is missing the calls fail with CIAO_ERR_HIP.
 
 #include <dlfcn.h>
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -912,6 +913,44 @@ static int32_t objective_t(ciao_ctx *ctx, const ciao_problem *p, const ciao_prox
     return CIAO_OK;
 }
 
+// The certificate at x: (with av == NULL) one full pass that also sums the f_i(x) -- the monitor's extra scalar, armed for this
+// pass alone and left RAW in the workspace (obj_scale = 1: the division by N_total is made on the host exactly as objective_t
+// makes it, so F is bitwise ciao_objective's) -- then the reduction over the d coordinates, one copy, one synchronisation.
+template <typename T>
+static int32_t certificate_t(ciao_ctx *ctx, const ciao_problem *p, const ciao_prox_desc *g, const void *x, const void *av, double gamma,
+                             double *out_host)
+{
+    const size_t head = (size_t)CERT_WS_DOUBLES * sizeof(double);
+    CIAO_TRY(ensure(ctx, &ctx->cert, &ctx->cert_bytes, head + (av ? 0 : (size_t)p->d * sizeof(T))));
+    double *res = (double *)ctx->cert;   // [0..5) S0 S1 S2 M V, [7] = sum_i f_i(x)
+    const bool own_pass = !av;
+    if (own_pass) {
+        T *own = (T *)((char *)ctx->cert + head);
+        RowsArgs<T> a = rows_args<T>(p);
+        a.x1 = (const T *)x;
+        a.want_fval = 1;
+        ctx->rowdot_A = nullptr;
+        Epilogue<T> e = epi_zero<T>();
+        e.c_sum = a.invN;
+        e.av_out = own;
+        e.obj_out = res + 6;   // the epilogue writes obj_out[1]
+        e.obj_scale = 1.0;
+        CIAO_TRY(launch_rows<T>(ctx, RM_GRAD, a, e));
+        av = own;
+    }
+    CIAO_TRY(launch_cert<T>(ctx, p->d, g, x, av, gamma, res + 8, res));
+    double h[8];
+    CIAO_HIP(hipMemcpyAsync(h, res, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    CIAO_HIP(hipStreamSynchronize(ctx->stream));
+    if (own_pass) out_host[0] = h[7] / (double)p->N_total;   // (a caller's av: out_host[0] stays what the caller put there)
+    out_host[1] = h[2];
+    out_host[2] = sqrt(h[0]) / gamma;
+    out_host[3] = h[3];
+    out_host[4] = h[1];
+    out_host[5] = h[4];
+    return CIAO_OK;
+}
+
 }  // namespace ciao
 
 using namespace ciao;
@@ -971,6 +1010,7 @@ int32_t ciao_ctx_destroy(ciao_ctx *ctx)
     if (ctx->rowdot) (void)hipFree(ctx->rowdot);
     if (ctx->monx) (void)hipFree(ctx->monx);
     if (ctx->idxbuf) (void)hipFree(ctx->idxbuf);
+    if (ctx->cert) (void)hipFree(ctx->cert);
     if (ctx->scal) (void)hipFree(ctx->scal);
     if (ctx->errflag) (void)hipFree(ctx->errflag);
     if (ctx->peer_counter) (void)hipFree(ctx->peer_counter);
@@ -1528,6 +1568,19 @@ int32_t ciao_objective(ciao_ctx *ctx, const ciao_problem *p, const ciao_prox_des
     CIAO_TRY(check_pair(p, g));
     CIAO_REQUIRE(x && obj_host, "x or obj_host is NULL");
     return DISPATCH(p->dtype, objective_t, ctx, p, g, x, obj_host);
+}
+
+int32_t ciao_certificate(ciao_ctx *ctx, const ciao_problem *p, const ciao_prox_desc *g, const void *x, const void *av, double gamma,
+                         double *out_host)
+{
+    CIAO_ENTER(ctx);
+    CIAO_TRY(check_problem(ctx, p));
+    CIAO_TRY(check_prox(g));
+    CIAO_REQUIRE(p->loss != CIAO_LOSS_LS_COMPLEX && !(g && g->kind == CIAO_PROX_L1_COMPLEX),
+                 "the certificate covers real problems only (complex T: no device certificate)");
+    CIAO_REQUIRE(x && out_host, "x or out_host is NULL");
+    CIAO_REQUIRE(gamma > 0 && gamma <= 1.79769313486231570815e308, "gamma must be > 0 and finite");
+    return DISPATCH(p->dtype, certificate_t, ctx, p, g, x, av, gamma, out_host);
 }
 
 int32_t ciao_svrg_init(ciao_ctx *ctx, const ciao_problem *p, const void *x0, void *av, void *z, void *z_full, void *w)

@@ -55,6 +55,8 @@ struct ciao_ctx {
     size_t monx_bytes = 0;
     void *idxbuf = nullptr;            // spelled-out indices of row-block batches that run as a sequential chain
     size_t idxbuf_bytes = 0;
+    void *cert = nullptr;              // ciao_certificate: results, partial records, then the pass's own grad f(x)
+    size_t cert_bytes = 0;
     double *scal = nullptr;    // small device scratch for scalar reductions (4096 doubles)
     int *errflag = nullptr;    // sticky device error word (out-of-range index)
 

@@ -112,6 +112,12 @@ int32_t long_plan(ciao_ctx *ctx, int mode, int64_t d, int64_t nrows, int *J, int
 template <typename T>
 int32_t launch_long(ciao_ctx *ctx, int mode, int J, int S, int C, RowsArgs<T> &a);
 
+// the certificate's reduction over the d coordinates (cert_kernels.h): five doubles into `out`; rec = workspace of CERT_GRID_CAP records.
+// Specialised in cert_f32.hip / cert_f64.hip.
+constexpr int CERT_WS_DOUBLES = 8 + 512 * 8;   // the results' block + CERT_GRID_CAP * CERT_REC (cert_kernels.h asserts the product)
+template <typename T>
+int32_t launch_cert(ciao_ctx *ctx, int64_t d, const ciao_prox_desc *g, const void *x, const void *av, double gamma, double *rec, double *out);
+
 // ProShI agent rows (init or one batch) + finalize + epilogue.  Specialised in rows_f32.hip / rows_f64.hip.
 template <typename T>
 int32_t launch_proshi(ciao_ctx *ctx, bool init, ProshiArgs<T> &a, const Epilogue<T> &ep);

@@ -371,6 +371,22 @@ class Context:
         L.check(self.lib.ciao_objective(self._h, p.ref, g.ref, self._vec(x, p, "x"), C.byref(out)))
         return out.value
 
+    def certificate(self, F, g, x, gamma: float, av=None, fval: float | None = None):
+        """Optimality certificate at x (include/ciao_hip.h: ciao_certificate) -> certificate.CertificateResult; synchronises.
+
+        av=None: one full pass is made (F(x) and grad f(x) together).  av = the caller's grad f(x) (SVRG: state.av where
+        x = z_full): no pass over A; F(x) is then `fval` where the caller knows it and nan otherwise -- and with it `objective`
+        and `gap`.  The gap is the lasso's (LeastSquares rows, NormL1(mu), mu > 0) and nan elsewhere: the logistic dual needs
+        per-sample terms.  Real problems only; the sharing family has no certificate."""
+        from .certificate import assemble
+        if isinstance(F, PackedSepQuad):
+            raise L.CiaoError(L.ERR_ARG, "the certificate covers finite sums of LeastSquares / logistic rows, not the sharing problem")
+        out = (C.c_double * 6)(float("nan") if fval is None else float(fval))
+        L.check(self.lib.ciao_certificate(self._h, F.ref, g.ref if g is not None else None, self._vec(x, F, "x"),
+                                          None if av is None else self._vec(av, F, "av"), float(gamma), out))
+        mu = g.lam if (g is not None and F.loss == L.LOSS_LS and g.kind == L.PROX_L1) else None
+        return assemble(*out, mu=mu)
+
     # -- SVRG ------------------------------------------------------------------------------------------------------------
     def svrg_init(self, p, x0, av, z, z_full, w):
         L.check(self.lib.ciao_svrg_init(self._h, p.ref, self._vec(x0, p, "x0"), self._vec(av, p, "av"), self._vec(z, p, "z"),

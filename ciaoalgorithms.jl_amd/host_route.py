@@ -337,6 +337,29 @@ def host_solution(state):
     return state.z_full if isinstance(state, HostSVRGState) else state.z
 
 
+def host_certificate(F, g, x, gamma, N):
+    """certificate.CertificateResult at x in numpy (float64): the quantities of ciao_certificate for operator objects -- the host
+    route's answer to certificate.Certificate.  The gap applies when every f_i is a LeastSquares and g = NormL1(mu), mu > 0."""
+    from . import operators as Op
+    from .certificate import assemble
+    x = np.asarray(x.detach().cpu() if hasattr(x, "detach") else x).reshape(-1).astype(np.float64)
+    F = [None] * int(N) if F is None else list(F)
+    av, fsum = np.zeros_like(x), 0.0
+    for f in F:
+        y, fx = H.gradient(f, x)
+        av += y
+        fsum += float(np.real(fx))
+    av /= max(len(F), 1)
+    r = x - H.prox(g, x - gamma * av, gamma)[0]
+    viol = 0.0
+    if isinstance(g, Op.IndBox):
+        lo, hi = np.asarray(g.lo, dtype=np.float64), np.asarray(g.hi, dtype=np.float64)
+        viol = float(max(np.max(lo - x), np.max(x - hi), 0.0))
+    lasso = isinstance(g, Op.NormL1) and len(F) > 0 and all(isinstance(f, Op.LeastSquares) for f in F)
+    return assemble(fsum / max(len(F), 1), _gval(g, x), float(np.linalg.norm(r)) / gamma, float(np.max(np.abs(av))) if x.size else 0.0,
+                    float(x @ av), viol, mu=float(g.lam) if lasso else None)
+
+
 def announce(why):
     warnings.warn("CIAOAlgorithms (AMD): this problem runs on the HOST route -- numpy, one operator call per sample, no GPU -- "
                   f"because {why}.  It is orders of magnitude slower than the device path and none of this package's "

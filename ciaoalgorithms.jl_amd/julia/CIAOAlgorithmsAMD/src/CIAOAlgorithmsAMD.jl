@@ -308,6 +308,30 @@ const TRUST_SVRG_STATE = Ref(false)
 to_dev_idx(idx::AbstractVector{<:Integer}) = ROCArray(Int64.(idx) .- 1)
 
 # ======================================================================================================================
+# Optimality certificate  (include/ciao_hip.h: ciao_certificate; Python twin: device.Context.certificate, certificate.py)
+# ======================================================================================================================
+# How far is x from the optimum?  One full pass (F(x) and ∇f(x) together; or the caller's `av` = ∇f(x), no pass) and one
+# reduction over the d coordinates:  residual = ‖x − prox_{γg}(x − γ∇f(x))‖/γ for every loss and prox here;  for LeastSquares rows
+# with g = NormL1(μ), μ > 0 the duality gap F + g − D at the dual point θ = s(λ/N)(Ax − b), s = min(1, μ/‖∇f‖∞):
+# D = F(2s − s²) − s·x'∇f (DESIGN.md section 8.6), so objective(x) − min ≤ gap for ANY x.  Elsewhere gap = NaN (the logistic dual
+# needs per-sample terms).  `fval`: F(x) where the caller knows it and passes `av`.  Not in the reference (`stop(state) = false`).
+function certificate(F::PackedF{R}, g::CiaoProxDesc, x::ROCArray{R,1}, γ::Real;
+                     av::Union{Nothing,ROCArray{R,1}} = nothing, fval::Real = NaN) where {R}
+    out = zeros(Float64, 6); out[1] = Float64(fval)
+    check(ccall((:ciao_certificate, libciao), Int32, (Ptr{Cvoid}, Ref{CiaoProblem}, Ref{CiaoProxDesc}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Float64}),
+                context().h, Ref(cproblem(F)), Ref(g), dptr(x), av === nothing ? C_NULL : dptr(av), Float64(γ), out))
+    Fv, gv, residual, grad_inf, x_dot_grad, viol = out
+    gval = viol > 0 ? Inf : gv
+    gap = NaN
+    if F.loss == LOSS_LS && g.kind == PROX_L1 && g.lam > 0
+        s = grad_inf == 0 ? 1.0 : min(1.0, g.lam / grad_inf)
+        gap = Fv + gval - (Fv * (2s - s^2) - s * x_dot_grad)
+    end
+    return (F = Fv, g = gval, objective = Fv + gval, residual = residual, grad_inf = grad_inf, x_dot_grad = x_dot_grad,
+            box_violation = viol, gap = gap)
+end
+
+# ======================================================================================================================
 # SVRG  (src/algorithms/SVRG/SVRG.jl, SVRG_basic.jl)
 # ======================================================================================================================
 struct SVRG{R<:Real}

@@ -197,6 +197,14 @@ CIAO_API int32_t ciao_proxgrad_step(ciao_ctx *ctx, const ciao_problem *p, const 
  * test/test_lasso.jl:45 computes it outside).  *obj_host receives the value (synchronises). */
 CIAO_API int32_t ciao_objective(ciao_ctx *ctx, const ciao_problem *p, const ciao_prox_desc *g, const void *x,
                        double *obj_host);
+/* Optimality certificate at x.  out_host[0] = F(x) = (1/N) sum f_i(x), [1] = g(x) (L1 value; 0 for Zero/Box),
+ * [2] = || x - prox_{gamma g}(x - gamma grad f(x)) ||_2 / gamma, [3] = || grad f(x) ||_inf, [4] = x . grad f(x),
+ * [5] = max Box violation of x (0 otherwise).  av: NULL -> one full pass is made here (the objective monitor's sum armed for it; the
+ * caller's monitor is neither read nor written); non-NULL -> the caller's grad f(x) is used, no pass over A, and out_host[0] is
+ * left as the caller set it (F(x) where known, NaN otherwise).  Real T only (complex problems are refused); gamma > 0, finite.
+ * The five reductions are bitwise reproducible: their order is a function of d alone.  Synchronises. */
+CIAO_API int32_t ciao_certificate(ciao_ctx *ctx, const ciao_problem *p, const ciao_prox_desc *g, const void *x,
+                                  const void *av, double gamma, double *out_host);
 
 /* ---- SVRG / SVRG++  (SVRG/SVRG_basic.jl) -------------------------------------------------------------------- */
 /* Base.iterate(iter), :57-66: av = full gradient at x0; z_full = x0; z = 0; w = x0. */
