@@ -229,11 +229,7 @@ static int32_t broadcast_from_owner(ciao_ctx *ctx, int64_t d, void *u, void *v, 
     } else {
         CIAO_HIP(hipMemsetAsync(buf, 0, 2 * bytes, ctx->stream));
     }
-    const int32_t hs = ctx->hook(ctx->hook_user, buf, 2 * d, sizeof(T) == 8 ? CIAO_F64 : CIAO_F32, (void *)ctx->stream);
-    if (hs != 0) {
-        set_error("all-reduce hook failed with status %d", hs);
-        return CIAO_ERR_HOOK;
-    }
+    CIAO_TRY(allreduce_hook(ctx, buf, 2 * d, sizeof(T) == 8 ? CIAO_F64 : CIAO_F32));
     CIAO_HIP(hipMemcpyAsync(u, buf, bytes, hipMemcpyDeviceToDevice, ctx->stream));
     CIAO_HIP(hipMemcpyAsync(v, buf + bytes, bytes, hipMemcpyDeviceToDevice, ctx->stream));
     return CIAO_OK;
@@ -462,6 +458,14 @@ struct BatchSrc {
     int64_t row0(int64_t t) const { return blocks() ? first[t] : 0; }
 };
 
+// the end of the run of consecutive batches that have batch t's size: [t, same_size_run) of the call's n batches
+static int64_t same_size_run(const BatchSrc &src, int64_t t, int64_t n)
+{
+    int64_t t1 = t + 1;
+    while (t1 < n && src.size(t1) == src.size(t)) ++t1;
+    return t1;
+}
+
 // Row blocks that run as a sequential chain need their indices spelled out on the device: first[t] .. first[t]+r-1 for
 // t in [t0, t1), r each, into the ctx's index workspace (host-built, one upload per run; pageable memory, so the copy is
 // complete when hipMemcpyAsync returns and the host buffer may go).
@@ -536,9 +540,7 @@ static int32_t finito_steps_t(ciao_ctx *ctx, const ciao_problem *p, const ciao_p
         const int64_t r = src.size(t);
         // on a row-sharded problem a batch may have no member on this rank: it still joins the all-reduce with a zero sum
         CIAO_REQUIRE(r >= 1 || (ctx->hook && r == 0), "Finito batch %lld is empty", (long long)t);
-        // a run of consecutive batches of the same size
-        int64_t t1 = t + 1;
-        while (t1 < nit && src.size(t1) == r) ++t1;
+        const int64_t t1 = same_size_run(src, t, nit);
         if (batch_as_chain<T>(ctx, p, r)) {
             ChainArgs<T> a = chain_args<T>(p, g);
             a.nsteps = (t1 - t) * r;
@@ -624,8 +626,7 @@ static int32_t lfinito_iterate_t(ciao_ctx *ctx, const ciao_problem *p, const cia
     while (t < nb) {
         const int64_t r = src.size(t);
         CIAO_REQUIRE(r >= 1 || (ctx->hook && r == 0), "LFinito batch %lld is empty", (long long)t);
-        int64_t t1 = t + 1;
-        while (t1 < nb && src.size(t1) == r) ++t1;
+        const int64_t t1 = same_size_run(src, t, nb);
         if (batch_as_chain<T>(ctx, p, r)) {
             ChainArgs<T> a = chain_args<T>(p, g);
             a.nsteps = (t1 - t) * r;
@@ -757,11 +758,7 @@ static int32_t afinito_steps_t(ciao_ctx *ctx, const ciao_problem *p, const ciao_
             t[0] = (double)hgv, t[1] = (double)c[0], t[2] = (double)c[1];
         }
         CIAO_HIP(hipMemcpyAsync(ctx->scal, t, sizeof t, hipMemcpyHostToDevice, ctx->stream));
-        const int32_t hs = ctx->hook(ctx->hook_user, ctx->scal, 3, CIAO_F64, (void *)ctx->stream);
-        if (hs != 0) {
-            set_error("all-reduce hook failed with status %d", hs);
-            return CIAO_ERR_HOOK;
-        }
+        CIAO_TRY(allreduce_hook(ctx, ctx->scal, 3, CIAO_F64));
         CIAO_HIP(hipMemcpyAsync(t, ctx->scal, sizeof t, hipMemcpyDeviceToHost, ctx->stream));
         CIAO_HIP(hipStreamSynchronize(ctx->stream));
         const T hgv = (T)t[0];
@@ -774,10 +771,11 @@ static int32_t afinito_steps_t(ciao_ctx *ctx, const ciao_problem *p, const ciao_
     return CIAO_OK;
 }
 
-template <typename T>
-static ProshiArgs<T> proshi_args(const ciao_sepquad *f, const void *gam, void *table)
+// what the batch-parallel kernels' ProshiArgs and the chain's ProshiChainArgs have in common
+template <typename T, template <typename> class Args>
+static Args<T> proshi_args(const ciao_sepquad *f, const void *gam, void *table)
 {
-    ProshiArgs<T> a{};
+    Args<T> a{};
     a.Q = (const T *)f->Q;
     a.q = (const T *)f->q;
     a.ld = f->ld;
@@ -789,7 +787,6 @@ static ProshiArgs<T> proshi_args(const ciao_sepquad *f, const void *gam, void *t
     a.gam = (const T *)gam;
     a.invN = T(1) / (T)f->N_total;
     a.table = (T *)table;
-    a.dense = f->dense;
     return a;
 }
 
@@ -797,7 +794,8 @@ template <typename T>
 static int32_t proshi_init_t(ciao_ctx *ctx, const ciao_sepquad *f, const ciao_prox_desc *g, const void *gam, const void *x0,
                              void *table, void *av, void *z, void *hat_gamma_dev)
 {
-    ProshiArgs<T> a = proshi_args<T>(f, gam, table);
+    ProshiArgs<T> a = proshi_args<T, ProshiArgs>(f, gam, table);
+    a.dense = f->dense;
     a.x = (const T *)x0;
     a.nrows = f->N;
     a.idx = nullptr;
@@ -826,44 +824,22 @@ static int32_t proshi_steps_t(ciao_ctx *ctx, const ciao_sepquad *f, const ciao_p
         // batch-parallel iteration 6.1-6.7 us whatever r.
         const int64_t lim = ctx->proshi_chain_max_batch >= 0 ? ctx->proshi_chain_max_batch : 18;
         if (!ctx->hook && !f->dense && r >= 1 && r <= lim) {
-            int64_t t1 = t + 1;
-            while (t1 < nit && src.size(t1) == r) ++t1;
-            ProshiChainArgs<T> c{};
-            c.Q = (const T *)f->Q;
-            c.q = (const T *)f->q;
-            c.ld = f->ld;
-            c.d = f->d;
-            c.N = f->N;
-            c.eta = (T)f->eta;
-            c.lo = (T)f->lo;
-            c.hi = (T)f->hi;
-            c.gam = (const T *)gam;
-            c.invN = T(1) / (T)f->N_total;
+            const int64_t t1 = same_size_run(src, t, nit);
+            ProshiChainArgs<T> c = proshi_args<T, ProshiChainArgs>(f, gam, table);
             c.hat_gamma = (T)hat_gamma;
             c.idx = src.idx(t);
             if (src.blocks()) CIAO_TRY(block_indices(ctx, src, t, t1, r, &c.idx));
             c.nvisits = (t1 - t) * r;
             c.batch = r;
             c.g = make_prox<T>(g);
-            c.table = (T *)table;
             c.av = (T *)av;
             c.z = (T *)z;
-            c.errflag = ctx->errflag;
-            const int64_t grid = (f->d + 255) / 256;
-            constexpr size_t lds = proshi_chain_lds_bytes<T>();
-            auto kern = &proshi_chain_kernel<T>;
-            if (lds > 60 * 1024)
-                CIAO_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, ctx->stream, c);
-            CIAO_HIP(hipGetLastError());
-            char nm[128];
-            snprintf(nm, sizeof nm, "proshi_chain_kernel<%s> grid=%lld block=256 visits=%lld batch=%lld", sizeof(T) == 8 ? "f64" : "f32",
-                     (long long)grid, (long long)c.nvisits, (long long)r);
-            ctx->last_kernel = nm;
+            CIAO_TRY(launch_proshi_chain<T>(ctx, c));
             t = t1 - 1;
             continue;
         }
-        ProshiArgs<T> a = proshi_args<T>(f, gam, table);
+        ProshiArgs<T> a = proshi_args<T, ProshiArgs>(f, gam, table);
+        a.dense = f->dense;
         a.x = (const T *)z;
         a.nrows = r;
         a.idx = src.idx(t);
@@ -1709,11 +1685,7 @@ int32_t ciao_hat_gamma(ciao_ctx *ctx, int32_t dtype, int64_t N, const void *gam,
     for (int i = 0; i < nb; ++i) s += part_data[i];
     if (ctx->hook) {
         CIAO_HIP(hipMemcpyAsync(ctx->scal, &s, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        const int32_t hs = ctx->hook(ctx->hook_user, ctx->scal, 1, CIAO_F64, (void *)ctx->stream);
-        if (hs != 0) {
-            set_error("all-reduce hook failed with status %d", hs);
-            return CIAO_ERR_HOOK;
-        }
+        CIAO_TRY(allreduce_hook(ctx, ctx->scal, 1, CIAO_F64));
         CIAO_HIP(hipMemcpyAsync(&s, ctx->scal, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         CIAO_HIP(hipStreamSynchronize(ctx->stream));
     }

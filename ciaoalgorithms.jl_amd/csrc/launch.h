@@ -26,6 +26,17 @@ inline PeerDev peer_dev(ciao_ctx *ctx)
     return p;
 }
 
+// the all-reduce hook over `count` elements of `buf` (device memory), in order on the ctx's stream
+inline int32_t allreduce_hook(ciao_ctx *ctx, void *buf, int64_t count, int32_t dtype)
+{
+    const int32_t hs = ctx->hook(ctx->hook_user, buf, count, dtype, (void *)ctx->stream);
+    if (hs != 0) {
+        set_error("all-reduce hook failed with status %d", hs);
+        return CIAO_ERR_HOOK;
+    }
+    return CIAO_OK;
+}
+
 // An open chain batch (ciao_ctx_chain_batch_begin): the launch of a chain kernel is RECORDED -- kernel, block, LDS, argument block,
 // the byte ranges of its state and which of them it writes -- and made by ciao_ctx_chain_batch_end, one launch per kernel with one
 // workgroup per chain.  Only the chains without a Finito batch structure are taken (SVRG inner cycles, SAGA / SAG steps).
@@ -121,6 +132,9 @@ int32_t launch_cert(ciao_ctx *ctx, int64_t d, const ciao_prox_desc *g, const voi
 // ProShI agent rows (init or one batch) + finalize + epilogue.  Specialised in rows_f32.hip / rows_f64.hip.
 template <typename T>
 int32_t launch_proshi(ciao_ctx *ctx, bool init, ProshiArgs<T> &a, const Epilogue<T> &ep);
+// a run of equal-sized small ProShI batches as one coordinate-parallel launch (proshi_chain_kernel).  Specialised there too.
+template <typename T>
+int32_t launch_proshi_chain(ciao_ctx *ctx, ProshiChainArgs<T> &c);
 // adaptive Finito chain (one sample per step, backtracking).  Specialised in chain_f32.hip / chain_f64.hip.
 template <typename T>
 int32_t launch_afinito(ciao_ctx *ctx, int loss, AFinitoArgs<T> &a);

@@ -55,6 +55,16 @@ int32_t launch_fast(ciao_ctx *ctx, int K, int grid, RowsArgs<T> &a)
     return launch_fast_pf<T, MODE, 0>(ctx, K, grid, a);
 }
 
+// one launch with dynamic LDS: above the default 64 KiB the ceiling has to be raised per kernel (160 KiB per CU on gfx950)
+template <typename Args>
+int32_t launch_with_lds(ciao_ctx *ctx, void (*kern)(Args), int64_t grid, int block, size_t lds, Args &a)
+{
+    if (lds > 60 * 1024)
+        CIAO_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(block), lds, ctx->stream, a);
+    return CIAO_OK;
+}
+
 template <typename T, int MODE>
 int32_t launch_generic(ciao_ctx *ctx, int nw, int grid, size_t lds, RowsArgs<T> &a)
 {
@@ -62,19 +72,8 @@ int32_t launch_generic(ciao_ctx *ctx, int nw, int grid, size_t lds, RowsArgs<T> 
         hipLaunchKernelGGL((rows_generic_kernel<T, 4, MODE, true>), dim3(grid), dim3(4 * WAVE), 0, ctx->stream, a);
         return CIAO_OK;
     }
-    // above the default 64 KiB the dynamic-LDS ceiling has to be raised per kernel (160 KiB per CU on gfx950)
-    if (nw == 4) {
-        if (lds > 60 * 1024)
-            CIAO_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&rows_generic_kernel<T, 4, MODE>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((rows_generic_kernel<T, 4, MODE>), dim3(grid), dim3(4 * WAVE), lds, ctx->stream, a);
-    } else {
-        if (lds > 60 * 1024)
-            CIAO_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&rows_generic_kernel<T, 1, MODE>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((rows_generic_kernel<T, 1, MODE>), dim3(grid), dim3(WAVE), lds, ctx->stream, a);
-    }
-    return CIAO_OK;
+    if (nw == 4) return launch_with_lds(ctx, &rows_generic_kernel<T, 4, MODE>, grid, 4 * WAVE, lds, a);
+    return launch_with_lds(ctx, &rows_generic_kernel<T, 1, MODE>, grid, WAVE, lds, a);
 }
 
 template <typename T, int MODE>
@@ -168,14 +167,7 @@ int32_t finish_reduction(ciao_ctx *ctx, int64_t d, int grid, int64_t pstride, co
         CIAO_FINALIZE(
                            (const T *)ctx->partial, pstride, grid, (const T *)ctx->pextra, d, (T *)ctx->sumbuf, ep, nopeers);
         CIAO_HIP(hipGetLastError());
-        if (ctx->hook) {
-            const int32_t hs = ctx->hook(ctx->hook_user, ctx->sumbuf, d + 1, sizeof(T) == 8 ? CIAO_F64 : CIAO_F32,
-                                         (void *)ctx->stream);
-            if (hs != 0) {
-                set_error("all-reduce hook failed with status %d", hs);
-                return CIAO_ERR_HOOK;
-            }
-        }
+        if (ctx->hook) CIAO_TRY(allreduce_hook(ctx, ctx->sumbuf, d + 1, sizeof(T) == 8 ? CIAO_F64 : CIAO_F32));
         if (!raw_only)
             hipLaunchKernelGGL((epilogue_kernel<T>), dim3((unsigned)((d + 255) / 256)), dim3(256), 0, ctx->stream,
                                (const T *)ctx->sumbuf, d, ep);
@@ -188,6 +180,21 @@ int32_t finish_reduction(ciao_ctx *ctx, int64_t d, int grid, int64_t pstride, co
 }
 #undef CIAO_FINALIZE
 
+// the workspace of a launch that leaves nparts partial d-vectors (and an extra scalar each) for finish_reduction: grown on
+// demand, the kernel's arguments (RowsArgs or ProshiArgs) pointed at it; the partials' stride is a.pstride
+template <typename Args>
+int32_t reduction_workspace(ciao_ctx *ctx, int64_t d, int64_t nparts, Args &a)
+{
+    using T = CIAO_T;
+    a.pstride = (d + 63) / 64 * 64;
+    CIAO_TRY(ensure(ctx, &ctx->partial, &ctx->partial_bytes, (size_t)nparts * (size_t)a.pstride * sizeof(T)));
+    CIAO_TRY(ensure(ctx, &ctx->pextra, &ctx->pextra_bytes, (size_t)nparts * sizeof(T)));
+    CIAO_TRY(ensure(ctx, &ctx->sumbuf, &ctx->sumbuf_bytes, (size_t)(d + 1) * sizeof(T)));
+    a.partial = (T *)ctx->partial;
+    a.pextra = (T *)ctx->pextra;
+    a.errflag = ctx->errflag;
+    return CIAO_OK;
+}
 
 // ---- which kernel, on what grid ------------------------------------------------------------------------------------------
 // The five families, in the order they are tried:
@@ -651,21 +658,11 @@ int32_t timing_begin(ciao_ctx *ctx, hipEvent_t *stop)
 // ctx->sumbuf[0..d) with the extra scalar at [d]; no epilogue.
 int32_t launch_rows_impl(ciao_ctx *ctx, int mode, RowsArgs<CIAO_T> &a, const Epilogue<CIAO_T> &ep, bool raw_only)
 {
-    using T = CIAO_T;
     const int64_t d = a.d;
     RowsPlan pl;
     CIAO_TRY(plan_rows(ctx, mode, a, pl));
-
-    // ---- workspace ---------------------------------------------------------------------------------------------------
-    const int64_t pstride = (d + 63) / 64 * 64;
     const int64_t nparts = pl.kind == RK_LONG ? pl.long_C : pl.grid * pl.parts_per_block;
-    CIAO_TRY(ensure(ctx, &ctx->partial, &ctx->partial_bytes, (size_t)nparts * (size_t)pstride * sizeof(T)));
-    CIAO_TRY(ensure(ctx, &ctx->pextra, &ctx->pextra_bytes, (size_t)nparts * sizeof(T)));
-    CIAO_TRY(ensure(ctx, &ctx->sumbuf, &ctx->sumbuf_bytes, (size_t)(d + 1) * sizeof(T)));
-    a.partial = (T *)ctx->partial;
-    a.pstride = pstride;
-    a.pextra = (T *)ctx->pextra;
-    a.errflag = ctx->errflag;
+    CIAO_TRY(reduction_workspace(ctx, d, nparts, a));
 
     hipEvent_t ev1 = nullptr;
     CIAO_TRY(timing_begin(ctx, &ev1));
@@ -673,7 +670,7 @@ int32_t launch_rows_impl(ciao_ctx *ctx, int mode, RowsArgs<CIAO_T> &a, const Epi
     CIAO_HIP(hipGetLastError());
     if (ev1) CIAO_HIP(hipEventRecord(ev1, ctx->stream));
     ctx->last_kernel = rows_kernel_name(ctx, mode, pl);
-    return finish_reduction(ctx, d, (int)nparts, pstride, ep, raw_only);
+    return finish_reduction(ctx, d, (int)nparts, a.pstride, ep, raw_only);
 }
 }  // namespace
 
@@ -691,135 +688,140 @@ int32_t launch_rows_raw<CIAO_T>(ciao_ctx *ctx, int mode, RowsArgs<CIAO_T> &a)
     return launch_rows_impl(ctx, mode, a, ep, true);
 }
 
-
+// ---- ProShI: agent rows of a separable quadratic (proshi_kernels.h) --------------------------------------------------------
 namespace {
-template <typename T, bool INIT, int NW>
-int32_t launch_proshi_nw(ciao_ctx *ctx, int64_t grid, size_t lds, ProshiArgs<T> &a)
-{
-    auto kern = &proshi_rows_kernel<T, INIT, NW>;
-    if (lds > 60 * 1024)
-        CIAO_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * WAVE), lds, ctx->stream, a);
-    return CIAO_OK;
-}
-}  // namespace
+enum ProshiKind { PK_DENSE, PK_VEC, PK_ROWS };
 
-namespace {
-template <typename T, bool INIT>
-int32_t launch_proshi_vec(ciao_ctx *ctx, int J, int64_t grid, ProshiArgs<T> &a)
-{
-    switch (J) {
-        case 1: hipLaunchKernelGGL((proshi_vec_kernel<T, INIT, 1>), dim3((unsigned)grid), dim3(256), 0, ctx->stream, a); break;
-        case 2: hipLaunchKernelGGL((proshi_vec_kernel<T, INIT, 2>), dim3((unsigned)grid), dim3(256), 0, ctx->stream, a); break;
-        case 4: hipLaunchKernelGGL((proshi_vec_kernel<T, INIT, 4>), dim3((unsigned)grid), dim3(256), 0, ctx->stream, a); break;
-        case 8: hipLaunchKernelGGL((proshi_vec_kernel<T, INIT, 8>), dim3((unsigned)grid), dim3(256), 0, ctx->stream, a); break;
-        default: set_error("internal: bad J %d", J); return CIAO_ERR_UNSUPPORTED;
-    }
-    return CIAO_OK;
-}
-}  // namespace
+struct ProshiPlan {
+    ProshiKind kind = PK_ROWS;
+    int J = 0;             // VEC: 16-byte chunks per thread
+    int nw = 0;            // ROWS: waves per block
+    size_t lds = 0;        // DENSE / ROWS: dynamic LDS bytes
+    int64_t grid = 1;      // workgroups, each leaving one partial d-vector
+    int block = 256;
+    bool timed = true;     // timing events around the launch
+};
 
-template <>
-int32_t launch_proshi<CIAO_T>(ciao_ctx *ctx, bool init, ProshiArgs<CIAO_T> &a, const Epilogue<CIAO_T> &ep)
+int32_t plan_proshi(const ciao_ctx *ctx, const ProshiArgs<CIAO_T> &a, ProshiPlan &pl)
 {
     using T = CIAO_T;
     const int64_t d = a.d;
+    constexpr int64_t PV = 16 / sizeof(T);
+    int64_t cap;
     if (a.dense) {
-        const size_t lds = (size_t)d * sizeof(T);
-        if (lds > 64 * 1024) {
+        pl.kind = PK_DENSE;
+        pl.lds = (size_t)d * sizeof(T);
+        if (pl.lds > 64 * 1024) {
             set_error("ProShI with dense Quadratic terms covers d*%zu bytes <= 64 KiB (got d=%lld)", sizeof(T), (long long)d);
             return CIAO_ERR_UNSUPPORTED;
         }
-        int64_t grid = a.nrows;
-        const int64_t cap = (int64_t)ctx->num_cu * 4;
-        if (grid > cap) grid = cap;
-        if (grid < 1) grid = 1;
-        const int64_t pstride = (d + 63) / 64 * 64;
-        CIAO_TRY(ensure(ctx, &ctx->partial, &ctx->partial_bytes, (size_t)grid * (size_t)pstride * sizeof(T)));
-        CIAO_TRY(ensure(ctx, &ctx->pextra, &ctx->pextra_bytes, (size_t)grid * sizeof(T)));
-        CIAO_TRY(ensure(ctx, &ctx->sumbuf, &ctx->sumbuf_bytes, (size_t)(d + 1) * sizeof(T)));
-        a.partial = (T *)ctx->partial;
-        a.pstride = pstride;
-        a.pextra = (T *)ctx->pextra;
-        a.errflag = ctx->errflag;
-        hipEvent_t ev1 = nullptr;
-        CIAO_TRY(timing_begin(ctx, &ev1));
-        if (init)
-            hipLaunchKernelGGL((proshi_dense_kernel<T, true>), dim3((unsigned)grid), dim3(256), lds, ctx->stream, a);
-        else
-            hipLaunchKernelGGL((proshi_dense_kernel<T, false>), dim3((unsigned)grid), dim3(256), lds, ctx->stream, a);
-        CIAO_HIP(hipGetLastError());
-        if (ev1) CIAO_HIP(hipEventRecord(ev1, ctx->stream));
-        char nm[128];
-        snprintf(nm, sizeof nm, "proshi_dense_kernel<%s,%s> grid=%lld block=256", sizeof(T) == 8 ? "f64" : "f32", init ? "init" : "step",
-                 (long long)grid);
-        ctx->last_kernel = nm;
-        return finish_reduction(ctx, d, (int)grid, pstride, ep, false);
-    }
-    // ---- vectorised path: 16-byte aligned rows of at most 32 KiB ----
-    constexpr int64_t PV = 16 / sizeof(T);
-    if (!ctx->force_generic && d % PV == 0 && d / PV <= 8 * 256 && aligned16(a.Q) && aligned16(a.q) && aligned16(a.table) &&
-        aligned16(a.x) && (a.ld * (int64_t)sizeof(T)) % 16 == 0) {
+        pl.grid = a.nrows;
+        cap = (int64_t)ctx->num_cu * 4;
+    } else if (!ctx->force_generic && d % PV == 0 && d / PV <= 8 * 256 && aligned16(a.Q) && aligned16(a.q) && aligned16(a.table) &&
+               aligned16(a.x) && (a.ld * (int64_t)sizeof(T)) % 16 == 0) {
+        // ---- vectorised path: 16-byte aligned rows of at most 32 KiB ----
+        pl.kind = PK_VEC;
         const int64_t nch = d / PV;
-        const int J = nch <= 256 ? 1 : (nch <= 512 ? 2 : (nch <= 1024 ? 4 : 8));
+        pl.J = nch <= 256 ? 1 : (nch <= 512 ? 2 : (nch <= 1024 ? 4 : 8));
         // one agent row per workgroup; from eight agents per CU on, two workgroups per CU (each with the next agent's rows in flight:
         // r = 4096 at d = 1024 fp64 41.7 -> 35.8 us, r = 8192 78 -> 62; below that the second set of partials costs more than it hides)
-        int64_t grid = a.nrows;
+        pl.grid = a.nrows;
         // (rows of up to 2 KiB, batches of 4096 agents and more: four -- d = 256 fp64 r = 16 384 / 65 536 57.0 -> 44.2 / 188 -> 128 us; at 4 KiB and
         // beyond two stay best: profiles/r05_midrow_batches.txt)
         const int64_t auto_bpc = (d * (int64_t)sizeof(T) <= 2048 && a.nrows >= 4096) ? 4 : (a.nrows >= 8 * (int64_t)ctx->num_cu ? 2 : 1);
-        const int64_t cap = (int64_t)ctx->num_cu * (ctx->split_blocks_per_cu > 0 ? ctx->split_blocks_per_cu : auto_bpc);
-        if (grid > cap) grid = cap;
-        if (grid < 1) grid = 1;
-        const int64_t pstride = (d + 63) / 64 * 64;
-        CIAO_TRY(ensure(ctx, &ctx->partial, &ctx->partial_bytes, (size_t)grid * (size_t)pstride * sizeof(T)));
-        CIAO_TRY(ensure(ctx, &ctx->pextra, &ctx->pextra_bytes, (size_t)grid * sizeof(T)));
-        CIAO_TRY(ensure(ctx, &ctx->sumbuf, &ctx->sumbuf_bytes, (size_t)(d + 1) * sizeof(T)));
-        a.partial = (T *)ctx->partial;
-        a.pstride = pstride;
-        a.pextra = (T *)ctx->pextra;
-        a.errflag = ctx->errflag;
-        hipEvent_t ev1 = nullptr;
-        CIAO_TRY(timing_begin(ctx, &ev1));
-        CIAO_TRY((init ? launch_proshi_vec<T, true>(ctx, J, grid, a) : launch_proshi_vec<T, false>(ctx, J, grid, a)));
-        CIAO_HIP(hipGetLastError());
-        if (ev1) CIAO_HIP(hipEventRecord(ev1, ctx->stream));
-        char nm[128];
-        snprintf(nm, sizeof nm, "proshi_vec_kernel<%s,%s,J%d> grid=%lld block=256", sizeof(T) == 8 ? "f64" : "f32", init ? "init" : "step", J,
-                 (long long)grid);
-        ctx->last_kernel = nm;
-        return finish_reduction(ctx, d, (int)grid, pstride, ep, false);
+        cap = (int64_t)ctx->num_cu * (ctx->split_blocks_per_cu > 0 ? ctx->split_blocks_per_cu : auto_bpc);
+    } else {
+        pl.kind = PK_ROWS;
+        pl.timed = false;   // inherited behaviour: the generic kernel has never recorded timing events
+        const size_t per = (size_t)d * sizeof(T), lds_cap = 144 * 1024;
+        pl.nw = 4;
+        if (5 * per > lds_cap) pl.nw = 1;
+        pl.lds = (size_t)(1 + pl.nw) * per;
+        if (pl.lds > lds_cap) {
+            set_error("ProShI covers 2*d*%zu bytes <= 144 KiB of LDS (got d=%lld)", sizeof(T), (long long)d);
+            return CIAO_ERR_UNSUPPORTED;
+        }
+        pl.block = pl.nw * WAVE;
+        pl.grid = (a.nrows + pl.nw - 1) / pl.nw;
+        cap = (int64_t)ctx->num_cu * (pl.nw == 4 ? 2 : 8);
     }
-    const size_t per = (size_t)d * sizeof(T), lds_cap = 144 * 1024;
-    int nw = 4;
-    if (5 * per > lds_cap) nw = 1;
-    const size_t lds = (size_t)(1 + nw) * per;
-    if (lds > lds_cap) {
-        set_error("ProShI covers 2*d*%zu bytes <= 144 KiB of LDS (got d=%lld)", sizeof(T), (long long)d);
-        return CIAO_ERR_UNSUPPORTED;
+    if (pl.grid > cap) pl.grid = cap;
+    if (pl.grid < 1) pl.grid = 1;
+    return CIAO_OK;
+}
+
+template <bool INIT>
+int32_t dispatch_proshi_phase(ciao_ctx *ctx, const ProshiPlan &pl, ProshiArgs<CIAO_T> &a)
+{
+    using T = CIAO_T;
+    const dim3 grid((unsigned)pl.grid), block(pl.block);
+    switch (pl.kind) {
+        case PK_DENSE: hipLaunchKernelGGL((proshi_dense_kernel<T, INIT>), grid, block, pl.lds, ctx->stream, a); return CIAO_OK;
+        case PK_VEC:
+            switch (pl.J) {
+                case 1: hipLaunchKernelGGL((proshi_vec_kernel<T, INIT, 1>), grid, block, 0, ctx->stream, a); return CIAO_OK;
+                case 2: hipLaunchKernelGGL((proshi_vec_kernel<T, INIT, 2>), grid, block, 0, ctx->stream, a); return CIAO_OK;
+                case 4: hipLaunchKernelGGL((proshi_vec_kernel<T, INIT, 4>), grid, block, 0, ctx->stream, a); return CIAO_OK;
+                case 8: hipLaunchKernelGGL((proshi_vec_kernel<T, INIT, 8>), grid, block, 0, ctx->stream, a); return CIAO_OK;
+            }
+            set_error("internal: bad J %d", pl.J);
+            return CIAO_ERR_UNSUPPORTED;
+        default:
+            return pl.nw == 4 ? launch_with_lds(ctx, &proshi_rows_kernel<T, INIT, 4>, pl.grid, pl.block, pl.lds, a)
+                              : launch_with_lds(ctx, &proshi_rows_kernel<T, INIT, 1>, pl.grid, pl.block, pl.lds, a);
     }
-    int64_t grid = (a.nrows + nw - 1) / nw;
-    const int64_t cap = (int64_t)ctx->num_cu * (nw == 4 ? 2 : 8);
-    if (grid > cap) grid = cap;
-    if (grid < 1) grid = 1;
-    const int64_t pstride = (d + 63) / 64 * 64;
-    CIAO_TRY(ensure(ctx, &ctx->partial, &ctx->partial_bytes, (size_t)grid * (size_t)pstride * sizeof(T)));
-    CIAO_TRY(ensure(ctx, &ctx->pextra, &ctx->pextra_bytes, (size_t)grid * sizeof(T)));
-    CIAO_TRY(ensure(ctx, &ctx->sumbuf, &ctx->sumbuf_bytes, (size_t)(d + 1) * sizeof(T)));
-    a.partial = (T *)ctx->partial;
-    a.pstride = pstride;
-    a.pextra = (T *)ctx->pextra;
-    a.errflag = ctx->errflag;
-    if (init)
-        CIAO_TRY((nw == 4 ? launch_proshi_nw<T, true, 4>(ctx, grid, lds, a) : launch_proshi_nw<T, true, 1>(ctx, grid, lds, a)));
-    else
-        CIAO_TRY((nw == 4 ? launch_proshi_nw<T, false, 4>(ctx, grid, lds, a) : launch_proshi_nw<T, false, 1>(ctx, grid, lds, a)));
-    CIAO_HIP(hipGetLastError());
+}
+
+int32_t dispatch_proshi(ciao_ctx *ctx, bool init, const ProshiPlan &pl, ProshiArgs<CIAO_T> &a)
+{
+    return init ? dispatch_proshi_phase<true>(ctx, pl, a) : dispatch_proshi_phase<false>(ctx, pl, a);
+}
+
+std::string proshi_kernel_name(bool init, const ProshiPlan &pl)
+{
+    const char *ty = sizeof(CIAO_T) == 8 ? "f64" : "f32", *phase = init ? "init" : "step";
+    const long long grid = (long long)pl.grid;
     char buf[128];
-    snprintf(buf, sizeof buf, "proshi_rows_kernel<%s,%s,NW%d> grid=%lld block=%d", sizeof(T) == 8 ? "f64" : "f32",
-             init ? "init" : "step", nw, (long long)grid, nw * WAVE);
-    ctx->last_kernel = buf;
-    return finish_reduction(ctx, d, (int)grid, pstride, ep, false);
+    switch (pl.kind) {
+        case PK_DENSE: snprintf(buf, sizeof buf, "proshi_dense_kernel<%s,%s> grid=%lld block=%d", ty, phase, grid, pl.block); break;
+        case PK_VEC: snprintf(buf, sizeof buf, "proshi_vec_kernel<%s,%s,J%d> grid=%lld block=%d", ty, phase, pl.J, grid, pl.block); break;
+        default: snprintf(buf, sizeof buf, "proshi_rows_kernel<%s,%s,NW%d> grid=%lld block=%d", ty, phase, pl.nw, grid, pl.block);
+    }
+    return buf;
+}
+}  // namespace
+
+// plan -> workspace -> kernel -> finalize + epilogue, as launch_rows_impl
+template <>
+int32_t launch_proshi<CIAO_T>(ciao_ctx *ctx, bool init, ProshiArgs<CIAO_T> &a, const Epilogue<CIAO_T> &ep)
+{
+    ProshiPlan pl;
+    CIAO_TRY(plan_proshi(ctx, a, pl));
+    CIAO_TRY(reduction_workspace(ctx, a.d, pl.grid, a));
+
+    hipEvent_t ev1 = nullptr;
+    if (pl.timed) CIAO_TRY(timing_begin(ctx, &ev1));
+    CIAO_TRY(dispatch_proshi(ctx, init, pl, a));
+    CIAO_HIP(hipGetLastError());
+    if (ev1) CIAO_HIP(hipEventRecord(ev1, ctx->stream));
+    ctx->last_kernel = proshi_kernel_name(init, pl);
+    return finish_reduction(ctx, a.d, (int)pl.grid, a.pstride, ep, false);
+}
+
+// a run of small batches, one thread per coordinate: no partials, no finalize, no timing events
+template <>
+int32_t launch_proshi_chain<CIAO_T>(ciao_ctx *ctx, ProshiChainArgs<CIAO_T> &c)
+{
+    using T = CIAO_T;
+    c.errflag = ctx->errflag;
+    const int64_t grid = (c.d + 255) / 256;
+    CIAO_TRY(launch_with_lds(ctx, &proshi_chain_kernel<T>, grid, 256, proshi_chain_lds_bytes<T>(), c));
+    CIAO_HIP(hipGetLastError());
+    char nm[128];
+    snprintf(nm, sizeof nm, "proshi_chain_kernel<%s> grid=%lld block=256 visits=%lld batch=%lld", sizeof(T) == 8 ? "f64" : "f32",
+             (long long)grid, (long long)c.nvisits, (long long)c.batch);
+    ctx->last_kernel = nm;
+    return CIAO_OK;
 }
 
 }  // namespace ciao
