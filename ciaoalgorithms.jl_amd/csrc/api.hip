@@ -489,6 +489,23 @@ static int32_t block_indices(ciao_ctx *ctx, const BatchSrc &src, int64_t t0, int
     return CIAO_OK;
 }
 
+// chain_args of a Finito / LFinito chain run: the batches [t, t1) of r rows each as (t1 - t) * r dependent steps
+template <typename T>
+static int32_t chain_run_args(ciao_ctx *ctx, const ciao_problem *p, const ciao_prox_desc *g, const BatchSrc &src, int64_t t, int64_t t1, int64_t r,
+                              const void *gam, double hat_gamma, void *av, void *z, ChainArgs<T> &a)
+{
+    a = chain_args<T>(p, g);
+    a.nsteps = (t1 - t) * r;
+    a.idx = src.idx(t);
+    if (src.blocks()) CIAO_TRY(block_indices(ctx, src, t, t1, r, &a.idx));
+    a.batch = r;
+    a.gam = (const T *)gam;
+    a.hat_gamma = (T)hat_gamma;
+    a.av = (T *)av;
+    a.z = (T *)z;
+    return CIAO_OK;
+}
+
 // Batches of r samples: r dependent chain steps in one persistent workgroup, or one batch-parallel rows launch?
 // "chain_max_batch" >= 0 fixes the crossover; -1 (default) derives it from measurements on MI355X: a batch-parallel step
 // costs ~10 us of launches + latency whatever r (tools/finito_batch_time.py), a chain step 0.45-1.5 us growing with the row.
@@ -542,16 +559,9 @@ static int32_t finito_steps_t(ciao_ctx *ctx, const ciao_problem *p, const ciao_p
         CIAO_REQUIRE(r >= 1 || (ctx->hook && r == 0), "Finito batch %lld is empty", (long long)t);
         const int64_t t1 = same_size_run(src, t, nit);
         if (batch_as_chain<T>(ctx, p, r)) {
-            ChainArgs<T> a = chain_args<T>(p, g);
-            a.nsteps = (t1 - t) * r;
-            a.idx = src.idx(t);
-            if (src.blocks()) CIAO_TRY(block_indices(ctx, src, t, t1, r, &a.idx));
-            a.batch = r;
-            a.gam = (const T *)gam;
-            a.hat_gamma = (T)hat_gamma;
+            ChainArgs<T> a;
+            CIAO_TRY(chain_run_args<T>(ctx, p, g, src, t, t1, r, gam, hat_gamma, av, z, a));
             a.table = (T *)table;
-            a.av = (T *)av;
-            a.z = (T *)z;
             CIAO_TRY(launch_chain<T>(ctx, CA_FINITO, a));
         } else {
             auto one = [&](int64_t tt) -> int32_t {
@@ -628,15 +638,8 @@ static int32_t lfinito_iterate_t(ciao_ctx *ctx, const ciao_problem *p, const cia
         CIAO_REQUIRE(r >= 1 || (ctx->hook && r == 0), "LFinito batch %lld is empty", (long long)t);
         const int64_t t1 = same_size_run(src, t, nb);
         if (batch_as_chain<T>(ctx, p, r)) {
-            ChainArgs<T> a = chain_args<T>(p, g);
-            a.nsteps = (t1 - t) * r;
-            a.idx = src.idx(t);
-            if (src.blocks()) CIAO_TRY(block_indices(ctx, src, t, t1, r, &a.idx));
-            a.batch = r;
-            a.gam = (const T *)gam;
-            a.hat_gamma = hg;
-            a.av = (T *)av;
-            a.z = (T *)z;
+            ChainArgs<T> a;
+            CIAO_TRY(chain_run_args<T>(ctx, p, g, src, t, t1, r, gam, hat_gamma, av, z, a));
             a.zf = (T *)z_full;
             CIAO_TRY(launch_chain<T>(ctx, CA_LFINITO, a));
             z_ready = false;

@@ -15,8 +15,6 @@ int32_t launch_dma_jms(ciao_ctx *ctx, ChainArgs<T> &a)
     constexpr size_t lds = chain_dma_lds_bytes<T, J, ALG, NT, SHARDED>();
     static_assert(lds <= 160 * 1024, "LDS budget");
     auto kern = &chain_dma_kernel<T, J, ALG, LOSS, MASKED, NT, SHARDED>;
-    ctx->chain_last_block = NT;
-    ctx->chain_last_masked = MASKED;   // (the one-wave classes have their own exact sizes: 1 and 2 KiB)
     if (lds > 60 * 1024)
         CIAO_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     if (ctx->batch_open) return chain_batch_record<T, ALG>(ctx, reinterpret_cast<const void *>(kern), NT, lds, a);
@@ -27,7 +25,7 @@ int32_t launch_dma_jms(ciao_ctx *ctx, ChainArgs<T> &a)
 template <typename T, int ALG, int LOSS, int J, bool MASKED, int NT>
 int32_t launch_dma_jm(ciao_ctx *ctx, ChainArgs<T> &a)
 {
-    // the two chains that may run over a shard table (ciao_ctx_set_shards); never the single-wave kernels: launch_dma keeps a
+    // the two chains that may run over a shard table (ciao_ctx_set_shards); never the single-wave kernels: plan_chain keeps a
     // sharded problem on four waves (a problem that needs several GPUs does not have 2 KiB rows, and the variants cost build time)
     if constexpr ((ALG == CA_SVRG || ALG == CA_SAGA) && NT != 64) {
         if (a.nshards > 0) return launch_dma_jms<T, ALG, LOSS, J, MASKED, NT, true>(ctx, a);
@@ -45,44 +43,31 @@ int32_t launch_dma_j(ciao_ctx *ctx, bool masked, ChainArgs<T> &a)
     return masked ? launch_dma_jm<T, ALG, LOSS, J, true, NT>(ctx, a) : launch_dma_jm<T, ALG, LOSS, J, false, NT>(ctx, a);
 }
 
-// Four waves up to 16 KiB rows, eight waves for 32 KiB rows.  Measured (SVRG, fp64, us per update): 16 KiB rows 0.62 on four
-// waves vs 0.68 on eight (the exchange among eight waves costs more than halving the per-thread work saves); 32 KiB rows
-// 0.94 vs 0.86 in round 2, 0.755 vs 0.570 (cached row dots) in round 4 (profiles/r04_chain_32k_ab.txt).
 }  // namespace
 
+// the kernel class (J chunks per thread, NT threads, MASKED) is plan_chain's decision (chain_launch.inc); the six that exist:
 template <typename T, int ALG, int LOSS>
-int32_t launch_dma(ciao_ctx *ctx, int J256, bool masked, ChainArgs<T> &a)
+int32_t launch_dma(ciao_ctx *ctx, int J, int NT, bool masked, ChainArgs<T> &a)
 {
-    switch (J256) {   // J256 = row bytes / 4096 rounded up to a power of two
-        case 1: {
-            // Short rows (up to 2 KiB: d <= 256 fp64 / 512 fp32, the shapes of most tabular problems) run on ONE wave: a lane
-            // owns one or two 16-byte chunks as it does with four waves, but the reduced dot product reaches every lane through
-            // an SGPR and the LDS exchange -- write, lgkmcnt(0), barrier, read: a third of a four-wave step -- does not exist.
-            const int64_t rowb = a.d * (int64_t)sizeof(T);
-            const bool one_wave = !ctx->chain_four_waves && a.nshards == 0;
-            if (one_wave && rowb <= 1024) return launch_dma_j<T, ALG, LOSS, 1, 64>(ctx, rowb != 1024, a);
-            if (one_wave && rowb <= 2048) return launch_dma_j<T, ALG, LOSS, 2, 64>(ctx, rowb != 2048, a);
-            // (fp64 rows of 2-4 KiB ran on one wave with four chunks per lane until round 5 -- 10 % faster than four waves in round 3,
-            // 0.277 against 0.306 us; the four-wave step has shed more since: d = 512 fp64 SVRG 0.285 on four waves against 0.292 on
-            // one, d = 384 0.291 against 0.314, Finito r = 1 0.39 against 0.45 -- and the one-wave variant parked 84-92 VGPRs in AGPRs)
-            return launch_dma_j<T, ALG, LOSS, 1, 256>(ctx, masked, a);
-        }
-        case 2: return launch_dma_j<T, ALG, LOSS, 2, 256>(ctx, masked, a);
-        case 4: return launch_dma_j<T, ALG, LOSS, 4, 256>(ctx, masked, a);
-        case 8: return launch_dma_j<T, ALG, LOSS, 4, 512>(ctx, masked, a);
-        default: set_error("internal: bad J %d", J256); return CIAO_ERR_UNSUPPORTED;
+    switch (J * 1000 + NT) {
+        case 1064: return launch_dma_j<T, ALG, LOSS, 1, 64>(ctx, masked, a);    // one wave: rows of up to 1 KiB ...
+        case 2064: return launch_dma_j<T, ALG, LOSS, 2, 64>(ctx, masked, a);    // ... and up to 2 KiB
+        case 1256: return launch_dma_j<T, ALG, LOSS, 1, 256>(ctx, masked, a);   // four waves: 4, 8, 16 KiB
+        case 2256: return launch_dma_j<T, ALG, LOSS, 2, 256>(ctx, masked, a);
+        case 4256: return launch_dma_j<T, ALG, LOSS, 4, 256>(ctx, masked, a);
+        case 4512: return launch_dma_j<T, ALG, LOSS, 4, 512>(ctx, masked, a);   // eight waves: 32 KiB
+        default: set_error("internal: no chain_dma_kernel class J=%d NT=%d", J, NT); return CIAO_ERR_UNSUPPORTED;
     }
 }
 
-
 #ifndef CIAO_DMA_LOSS   // both losses in this unit
 #define CIAO_DMA_INST(AA)                                                                                   \
-    template int32_t launch_dma<CIAO_T, AA, CIAO_LOSS_LS>(ciao_ctx *, int, bool, ChainArgs<CIAO_T> &);      \
-    template int32_t launch_dma<CIAO_T, AA, CIAO_LOSS_LOGISTIC>(ciao_ctx *, int, bool, ChainArgs<CIAO_T> &);
+    template int32_t launch_dma<CIAO_T, AA, CIAO_LOSS_LS>(ciao_ctx *, int, int, bool, ChainArgs<CIAO_T> &);      \
+    template int32_t launch_dma<CIAO_T, AA, CIAO_LOSS_LOGISTIC>(ciao_ctx *, int, int, bool, ChainArgs<CIAO_T> &);
 #elif CIAO_DMA_LOSS == 0
-#define CIAO_DMA_INST(AA) template int32_t launch_dma<CIAO_T, AA, CIAO_LOSS_LS>(ciao_ctx *, int, bool, ChainArgs<CIAO_T> &);
+#define CIAO_DMA_INST(AA) template int32_t launch_dma<CIAO_T, AA, CIAO_LOSS_LS>(ciao_ctx *, int, int, bool, ChainArgs<CIAO_T> &);
 #else
-#define CIAO_DMA_INST(AA) template int32_t launch_dma<CIAO_T, AA, CIAO_LOSS_LOGISTIC>(ciao_ctx *, int, bool, ChainArgs<CIAO_T> &);
+#define CIAO_DMA_INST(AA) template int32_t launch_dma<CIAO_T, AA, CIAO_LOSS_LOGISTIC>(ciao_ctx *, int, int, bool, ChainArgs<CIAO_T> &);
 #endif
 #if CIAO_DMA_PART == 0
 CIAO_DMA_INST(CA_SVRG)

@@ -20,27 +20,15 @@ int32_t launch_ws_jmn(ciao_ctx *ctx, ChainArgs<T> &a)
     return CIAO_OK;
 }
 
-template <typename T, int ALG, int LOSS, int J>
-int32_t launch_ws_j(ciao_ctx *ctx, bool masked, ChainArgs<T> &a)
-{
-    // one issuer wave per 4 KiB of row per step at most (option chain_ws_issuers overrides: 1 or 2)
-    const int niss = ctx->chain_ws_issuers > 0 ? (int)ctx->chain_ws_issuers : 2;
-    ctx->chain_last_ws = niss;
-    if (niss == 1)
-        return masked ? launch_ws_jmn<T, ALG, LOSS, J, true, 1>(ctx, a) : launch_ws_jmn<T, ALG, LOSS, J, false, 1>(ctx, a);
-    return masked ? launch_ws_jmn<T, ALG, LOSS, J, true, 2>(ctx, a) : launch_ws_jmn<T, ALG, LOSS, J, false, 2>(ctx, a);
-}
 }  // namespace
 
+// rows of up to 4 KiB (J = 1; beyond, chain_dma_kernel is faster); the issuer count, 1 or 2, is plan_chain's decision (chain_launch.inc)
 template <typename T, int ALG, int LOSS>
-int32_t launch_ws(ciao_ctx *ctx, int J256, bool masked, ChainArgs<T> &a)
+int32_t launch_ws(ciao_ctx *ctx, int issuers, bool masked, ChainArgs<T> &a)
 {
-    switch (J256) {
-        case 1: return launch_ws_j<T, ALG, LOSS, 1>(ctx, masked, a);
-        default:   // rows beyond 4 KiB: chain_dma_kernel is faster (chain_launch.inc)
-            set_error("internal: bad J %d for the wave-specialised chain", J256);
-            return CIAO_ERR_UNSUPPORTED;
-    }
+    if (issuers == 1)
+        return masked ? launch_ws_jmn<T, ALG, LOSS, 1, true, 1>(ctx, a) : launch_ws_jmn<T, ALG, LOSS, 1, false, 1>(ctx, a);
+    return masked ? launch_ws_jmn<T, ALG, LOSS, 1, true, 2>(ctx, a) : launch_ws_jmn<T, ALG, LOSS, 1, false, 2>(ctx, a);
 }
 
 template int32_t launch_ws<CIAO_T, CIAO_WS_ALG, CIAO_LOSS_LS>(ciao_ctx *, int, bool, ChainArgs<CIAO_T> &);

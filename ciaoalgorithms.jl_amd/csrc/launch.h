@@ -74,19 +74,19 @@ int32_t launch_rows(ciao_ctx *ctx, int mode, RowsArgs<T> &a, const Epilogue<T> &
 // same, but leaves the reduced sum in ctx->sumbuf[0..d) and the extra scalar in ctx->sumbuf[d]; no epilogue.
 template <typename T>
 int32_t launch_rows_raw(ciao_ctx *ctx, int mode, RowsArgs<T> &a);
-// persistent single-workgroup chain.  Specialised in chain_f32.hip / chain_f64.hip.
+// the sequential chains: plan, launch (inside an open chain batch: record) and name.  Specialised in chain_f32.hip / chain_f64.hip.
 template <typename T>
 int32_t launch_chain(ciao_ctx *ctx, int alg, ChainArgs<T> &a);
 
-// the LDS-DMA fast chain for one (algorithm, loss); J256 = row bytes / 4096 rounded up to a power of two.  Defined in
-// chain_dma_launch.inc, instantiated in chain_dma{0..4}_f32/f64.hip.
+// the LDS-DMA fast chain for one (algorithm, loss) in the kernel class the chain plan chose: J chunks per thread of NT threads, one of
+// (1,64) (2,64) (1,256) (2,256) (4,256) (4,512).  Defined in chain_dma_launch.inc, instantiated in chain_dma{0..4}_f32/f64.hip.
 template <typename T, int ALG, int LOSS>
-int32_t launch_dma(ciao_ctx *ctx, int J256, bool masked, ChainArgs<T> &a);
+int32_t launch_dma(ciao_ctx *ctx, int J, int NT, bool masked, ChainArgs<T> &a);
 
 // the wave-specialised chain (chain_ws_kernels.h: consumer / stager / issuer waves, barrier-free exchange) for SAGA / SAG on rows
-// of up to 4 KiB.  Defined in chain_ws_launch.inc, instantiated in chain_ws1_f32/f64.hip.
+// of up to 4 KiB, with the issuer waves the chain plan chose (1 or 2).  Defined in chain_ws_launch.inc, instantiated in chain_ws1_f32/f64.hip.
 template <typename T, int ALG, int LOSS>
-int32_t launch_ws(ciao_ctx *ctx, int J256, bool masked, ChainArgs<T> &a);
+int32_t launch_ws(ciao_ctx *ctx, int issuers, bool masked, ChainArgs<T> &a);
 
 // complex chains on the LDS-DMA ring (chain_cdma_kernel): rows of whole 16-byte chunks up to 16 KiB.  Specialised in
 // chain_cdma_f32.hip / chain_cdma_f64.hip.
