@@ -10,7 +10,12 @@ one reduction over the d coordinates:
 The gap exists for LeastSquares rows with g = NormL1(mu), mu > 0: the dual point theta = s (lam/N)(Ax - b),
 s = min(1, mu / ||grad f(x)||_inf), is feasible by construction and b'r = x'A'r - ||r||^2 removes every per-row quantity, so that
 D = F (2s - s^2) - s x.grad f(x) needs only the numbers the d-vector reduction leaves.  For the logistic loss the dual value needs
-the per-sample terms (an entropy of every margin): no gap there, `gap` is nan and `residual` is the certificate.
+the per-sample terms (an entropy of every margin): without them `gap` is nan and `residual` is the certificate.  With
+`samples=True` the call keeps the row dots of its pass and a second reduction, over the N samples, adds them:
+
+    gap      = F(x) + g(x) + (1/N) sum_i h(s sigma(-y_i a_i'x))         logistic rows with g = NormL1(mu), mu > 0
+
+with h(u) = u log u + (1 - u) log(1 - u) and the lasso's s: the dual point u_i = s sigma(-t_i) is feasible by the same scaling.
 
     cert = Certificate(ctx, F, g, N, gamma)
     x, it = SVRG(...)(x0, F=F, g=g, N=N, stop=stop_when(cert, gap=1e-8), check_every=k)
@@ -34,12 +39,16 @@ class CertificateResult(NamedTuple):
     gap: float             # lasso duality gap (nan where it does not apply)
 
 
-def assemble(F, g_value, residual, grad_inf, x_dot_grad, box_violation, mu=None) -> CertificateResult:
-    """The named result from the six numbers of ciao_certificate, in double.  mu: NormL1's weight when the rows are LeastSquares
-    (the gap applies), else None."""
+def assemble(F, g_value, residual, grad_inf, x_dot_grad, box_violation, mu=None, entropy=None, n=None) -> CertificateResult:
+    """The named result from the six numbers of ciao_certificate, in double.  mu: NormL1's weight when the gap applies, else None:
+    for LeastSquares rows the lasso's gap; for logistic rows give also entropy = E(s), the per-sample reduction's sum of
+    h(s sigma(-t_i)) at s = min(1, mu / grad_inf), and n = the number of samples: gap = F + g + E / n."""
     g = math.inf if box_violation > 0 else g_value
     gap = math.nan
-    if mu is not None and mu > 0:
+    if entropy is not None:
+        if mu is not None and mu > 0:
+            gap = F + g + entropy / n
+    elif mu is not None and mu > 0:
         s = 1.0 if grad_inf == 0 else min(1.0, mu / grad_inf)
         dual = F * (2 * s - s * s) - s * x_dot_grad
         gap = F + g - dual
@@ -52,23 +61,24 @@ class Certificate:
     F, g, N: what the solver call takes (operator objects, or device.PackedF / device.ProxG); gamma: the prox-gradient step of the
     residual (any gamma > 0 certifies; 1 / L_max is the natural scale).  On a device state whose F came as operator objects the
     iterable's own packing of them is used (no second copy of A on the device); a host-route state (backend == "host") is answered
-    in numpy by host_route.host_certificate.  ctx=None: the state's context."""
+    in numpy by host_route.host_certificate.  ctx=None: the state's context.  samples=True: the per-sample terms too -- the duality
+    gap of logistic rows with NormL1 (Context.certificate's keyword)."""
 
-    def __init__(self, ctx, F, g, N, gamma):
+    def __init__(self, ctx, F, g, N, gamma, samples=False):
         if not (gamma > 0 and math.isfinite(gamma)):
             raise ValueError("gamma must be > 0 and finite")
-        self.ctx, self.F, self.g, self.N, self.gamma = ctx, F, g, int(N), float(gamma)
+        self.ctx, self.F, self.g, self.N, self.gamma, self.samples = ctx, F, g, int(N), float(gamma), bool(samples)
 
     def __call__(self, state) -> CertificateResult:
         from .solvers import solution
         x = solution(state)
         if getattr(state, "backend", None) == "host":
             from . import host_route as HR
-            return HR.host_certificate(self.F, self.g, x, self.gamma, self.N)
+            return HR.host_certificate(self.F, self.g, x, self.gamma, self.N, samples=self.samples)
         from .device import PackedF
         it = state._it
         F, g = (self.F, self.g) if isinstance(self.F, PackedF) else (it.F, it.g)
-        return (self.ctx if self.ctx is not None else it.ctx).certificate(F, g, x, self.gamma)
+        return (self.ctx if self.ctx is not None else it.ctx).certificate(F, g, x, self.gamma, samples=self.samples)
 
 
 def stop_when(cert, gap=None, residual=None):

@@ -892,6 +892,24 @@ static int32_t objective_t(ciao_ctx *ctx, const ciao_problem *p, const ciao_prox
     return CIAO_OK;
 }
 
+// The certificate's own pass (certificate_t below: want_fval, the raw sum of the f_i left at res[7], grad f(x) into `own`), optionally
+// with the row dots a_i'x written to `rowdot_out` (ciao_row_dots, ciao_certificate_samples).
+template <typename T>
+static int32_t samples_pass(ciao_ctx *ctx, const ciao_problem *p, const void *x, T *rowdot_out, double *res, T *own)
+{
+    RowsArgs<T> a = rows_args<T>(p);
+    a.x1 = (const T *)x;
+    a.want_fval = 1;
+    a.rowdot_out = rowdot_out;
+    ctx->rowdot_A = nullptr;   // a full pass: whatever the SVRG chain had cached belongs to an older one
+    Epilogue<T> e = epi_zero<T>();
+    e.c_sum = a.invN;
+    e.av_out = own;
+    e.obj_out = res + 6;   // the epilogue writes obj_out[1]
+    e.obj_scale = 1.0;
+    return launch_rows<T>(ctx, RM_GRAD, a, e);
+}
+
 // The certificate at x: (with av == NULL) one full pass that also sums the f_i(x) -- the monitor's extra scalar, armed for this
 // pass alone and left RAW in the workspace (obj_scale = 1: the division by N_total is made on the host exactly as objective_t
 // makes it, so F is bitwise ciao_objective's) -- then the reduction over the d coordinates, one copy, one synchronisation.
@@ -905,16 +923,7 @@ static int32_t certificate_t(ciao_ctx *ctx, const ciao_problem *p, const ciao_pr
     const bool own_pass = !av;
     if (own_pass) {
         T *own = (T *)((char *)ctx->cert + head);
-        RowsArgs<T> a = rows_args<T>(p);
-        a.x1 = (const T *)x;
-        a.want_fval = 1;
-        ctx->rowdot_A = nullptr;
-        Epilogue<T> e = epi_zero<T>();
-        e.c_sum = a.invN;
-        e.av_out = own;
-        e.obj_out = res + 6;   // the epilogue writes obj_out[1]
-        e.obj_scale = 1.0;
-        CIAO_TRY(launch_rows<T>(ctx, RM_GRAD, a, e));
+        CIAO_TRY(samples_pass<T>(ctx, p, x, (T *)nullptr, res, own));
         av = own;
     }
     CIAO_TRY(launch_cert<T>(ctx, p->d, g, x, av, gamma, res + 8, res));
@@ -927,6 +936,56 @@ static int32_t certificate_t(ciao_ctx *ctx, const ciao_problem *p, const ciao_pr
     out_host[3] = h[3];
     out_host[4] = h[1];
     out_host[5] = h[4];
+    return CIAO_OK;
+}
+
+// out[i] = a_i'x for the N local rows: the certificate's pass with rowdot_out = out; its d-vector stays in the workspace.
+template <typename T>
+static int32_t row_dots_t(ciao_ctx *ctx, const ciao_problem *p, const void *x, void *out)
+{
+    const size_t head = (size_t)MSTAT_WS_DOUBLES * sizeof(double);
+    CIAO_TRY(ensure(ctx, &ctx->cert, &ctx->cert_bytes, head + (size_t)p->d * sizeof(T)));
+    return samples_pass<T>(ctx, p, x, (T *)out, (double *)ctx->cert, (T *)((char *)ctx->cert + head));
+}
+
+// the per-sample reduction alone, over caller's dots: two kernels, one copy, one synchronisation
+template <typename T>
+static int32_t margin_stats_t(ciao_ctx *ctx, const ciao_problem *p, const void *dots, double s, double *out_host)
+{
+    CIAO_TRY(ensure(ctx, &ctx->cert, &ctx->cert_bytes, (size_t)MSTAT_WS_DOUBLES * sizeof(double)));
+    double *res = (double *)ctx->cert;
+    CIAO_TRY(launch_mstat<T>(ctx, p->loss, p->N, dots, p->b, s, nullptr, 0.0, res + 16, res + 8));
+    CIAO_HIP(hipMemcpyAsync(out_host, res + 8, 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    CIAO_HIP(hipStreamSynchronize(ctx->stream));
+    return CIAO_OK;
+}
+
+// The certificate with its per-sample terms: the certificate's pass with the row dots kept (ctx->rowdot: the SVRG chain's cache is
+// invalid from here on), the reduction over the d coordinates, then the reduction over the N samples with s formed on the device from
+// the first one's ||grad f||_inf -- no host round trip between the two --, one copy, one synchronisation.
+template <typename T>
+static int32_t certificate_samples_t(ciao_ctx *ctx, const ciao_problem *p, const ciao_prox_desc *g, const void *x, double gamma,
+                                     double *out_host)
+{
+    const size_t head = (size_t)MSTAT_WS_DOUBLES * sizeof(double);
+    CIAO_TRY(ensure(ctx, &ctx->cert, &ctx->cert_bytes, head + (size_t)p->d * sizeof(T)));
+    CIAO_TRY(ensure(ctx, &ctx->rowdot, &ctx->rowdot_bytes, (size_t)p->N * sizeof(T)));
+    double *res = (double *)ctx->cert;   // [0..5) S0 S1 S2 M V, [7] = sum_i f_i(x), [8..12) the four statistics, [16..) records
+    T *own = (T *)((char *)ctx->cert + head);
+    CIAO_TRY(samples_pass<T>(ctx, p, x, (T *)ctx->rowdot, res, own));
+    CIAO_TRY(launch_cert<T>(ctx, p->d, g, x, own, gamma, res + 16, res));
+    const bool scaled = g && g->kind == CIAO_PROX_L1 && g->lam > 0.0;
+    CIAO_TRY(launch_mstat<T>(ctx, p->loss, p->N, ctx->rowdot, p->b, 1.0, scaled ? res + 3 : nullptr, scaled ? g->lam : 0.0, res + 16, res + 8));
+    double h[12];
+    CIAO_HIP(hipMemcpyAsync(h, res, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    CIAO_HIP(hipStreamSynchronize(ctx->stream));
+    out_host[0] = h[7] / (double)p->N_total;
+    out_host[1] = h[2];
+    out_host[2] = sqrt(h[0]) / gamma;
+    out_host[3] = h[3];
+    out_host[4] = h[1];
+    out_host[5] = h[4];
+    for (int k = 0; k < 4; ++k) out_host[6 + k] = h[8 + k];
     return CIAO_OK;
 }
 
@@ -1560,6 +1619,49 @@ int32_t ciao_certificate(ciao_ctx *ctx, const ciao_problem *p, const ciao_prox_d
     CIAO_REQUIRE(x && out_host, "x or out_host is NULL");
     CIAO_REQUIRE(gamma > 0 && gamma <= 1.79769313486231570815e308, "gamma must be > 0 and finite");
     return DISPATCH(p->dtype, certificate_t, ctx, p, g, x, av, gamma, out_host);
+}
+
+static int32_t check_samples(const ciao_problem *p, const char *who)
+{
+    CIAO_REQUIRE(p->loss != CIAO_LOSS_LS_COMPLEX, "%s covers real problems only (complex T: no per-sample quantities on the device)", who);
+    CIAO_REQUIRE(p->loss != CIAO_LOSS_ZERO, "%s needs data rows (Zero() terms have no a_i'x)", who);
+    return CIAO_OK;
+}
+
+int32_t ciao_row_dots(ciao_ctx *ctx, const ciao_problem *p, const void *x, void *out)
+{
+    CIAO_ENTER(ctx);
+    CIAO_TRY(check_problem(ctx, p));
+    CIAO_TRY(check_samples(p, "ciao_row_dots"));
+    CIAO_REQUIRE(x && (out || p->N == 0), "x or out is NULL");
+    return DISPATCH(p->dtype, row_dots_t, ctx, p, x, out);
+}
+
+int32_t ciao_margin_stats(ciao_ctx *ctx, const ciao_problem *p, const void *dots, double s, double *out_host)
+{
+    CIAO_ENTER(ctx);
+    CIAO_TRY(check_problem(ctx, p));
+    CIAO_TRY(check_samples(p, "ciao_margin_stats"));
+    CIAO_REQUIRE(p->N >= 1, "ciao_margin_stats needs at least one sample (N = 0)");
+    CIAO_REQUIRE(dots && out_host, "dots or out_host is NULL");
+    CIAO_REQUIRE(s >= 0.0 && s <= 1.0, "the dual scaling s must lie in [0, 1] (got %g)", s);
+    return DISPATCH(p->dtype, margin_stats_t, ctx, p, dots, s, out_host);
+}
+
+int32_t ciao_certificate_samples(ciao_ctx *ctx, const ciao_problem *p, const ciao_prox_desc *g, const void *x, double gamma,
+                                 double *out_host)
+{
+    CIAO_ENTER(ctx);
+    CIAO_TRY(check_problem(ctx, p));
+    CIAO_TRY(check_prox(g));
+    CIAO_TRY(check_samples(p, "ciao_certificate_samples"));
+    CIAO_REQUIRE(!(g && g->kind == CIAO_PROX_L1_COMPLEX), "ciao_certificate_samples covers real problems only (complex prox)");
+    CIAO_REQUIRE(!ctx->hook && ctx->shards.nshards == 0,
+                 "ciao_certificate_samples on a row-sharded context: the per-sample sums would need an all-reduce of their own");
+    CIAO_REQUIRE(p->N >= 1, "ciao_certificate_samples needs at least one sample (N = 0)");
+    CIAO_REQUIRE(x && out_host, "x or out_host is NULL");
+    CIAO_REQUIRE(gamma > 0 && gamma <= 1.79769313486231570815e308, "gamma must be > 0 and finite");
+    return DISPATCH(p->dtype, certificate_samples_t, ctx, p, g, x, gamma, out_host);
 }
 
 int32_t ciao_svrg_init(ciao_ctx *ctx, const ciao_problem *p, const void *x0, void *av, void *z, void *z_full, void *w)

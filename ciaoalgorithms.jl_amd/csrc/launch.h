@@ -129,6 +129,15 @@ constexpr int CERT_WS_DOUBLES = 8 + 512 * 8;   // the results' block + CERT_GRID
 template <typename T>
 int32_t launch_cert(ciao_ctx *ctx, int64_t d, const ciao_prox_desc *g, const void *x, const void *av, double gamma, double *rec, double *out);
 
+// the per-sample reduction over the N row dots and targets (mstat_kernels.h): four doubles into `out`; rec = workspace of CERT_GRID_CAP
+// records.  s: the literal, or (M_dev non-null) formed on the device as M == 0 ? 1 : min(1, mu / M) with M = *M_dev.  Specialised in
+// mstat_f32.hip / mstat_f64.hip.  Workspace of the entry points that use it (ctx->cert): [0..8) the certificate's results, [8..16) these
+// four, then the records (the two reductions use them one after the other), then the pass's own grad f(x).
+constexpr int MSTAT_WS_DOUBLES = 16 + 512 * 8;
+template <typename T>
+int32_t launch_mstat(ciao_ctx *ctx, int loss, int64_t N, const void *dots, const void *b, double s, const double *M_dev, double mu,
+                     double *rec, double *out);
+
 // ProShI agent rows (init or one batch) + finalize + epilogue.  Specialised in rows_f32.hip / rows_f64.hip.
 template <typename T>
 int32_t launch_proshi(ciao_ctx *ctx, bool init, ProshiArgs<T> &a, const Epilogue<T> &ep);

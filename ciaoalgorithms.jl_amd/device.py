@@ -5,6 +5,7 @@ torch.distributed -- all arithmetic happens in libciao_hip.so.
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -179,6 +180,22 @@ class ProxG:
     @property
     def ref(self):
         return C.byref(self._c)
+
+
+class LogisticStats(NamedTuple):
+    """Context.margin_stats on logistic rows, t_i = y_i a_i'x."""
+    loss_sum: float     # sum_i log(1 + exp(-t_i))
+    entropy: float      # E(s) = sum_i h(s sigma(-t_i)), h(u) = u log u + (1 - u) log(1 - u)
+    errors: float       # the number of samples with t_i <= 0
+    min_margin: float   # min_i t_i
+
+
+class LeastSquaresStats(NamedTuple):
+    """Context.margin_stats on LeastSquares rows, r_i = a_i'x - b_i."""
+    sum_r2: float       # sum_i r_i^2
+    sum_b: float        # sum_i b_i
+    sum_b2: float       # sum_i b_i^2
+    max_abs_r: float    # max_i |r_i|
 
 
 class _ChainBatch:
@@ -371,21 +388,67 @@ class Context:
         L.check(self.lib.ciao_objective(self._h, p.ref, g.ref, self._vec(x, p, "x"), C.byref(out)))
         return out.value
 
-    def certificate(self, F, g, x, gamma: float, av=None, fval: float | None = None):
+    def certificate(self, F, g, x, gamma: float, av=None, fval: float | None = None, samples: bool = False):
         """Optimality certificate at x (include/ciao_hip.h: ciao_certificate) -> certificate.CertificateResult; synchronises.
 
         av=None: one full pass is made (F(x) and grad f(x) together).  av = the caller's grad f(x) (SVRG: state.av where
         x = z_full): no pass over A; F(x) is then `fval` where the caller knows it and nan otherwise -- and with it `objective`
         and `gap`.  The gap is the lasso's (LeastSquares rows, NormL1(mu), mu > 0) and nan elsewhere: the logistic dual needs
-        per-sample terms.  Real problems only; the sharing family has no certificate."""
+        per-sample terms.  Real problems only; the sharing family has no certificate.
+
+        samples=True (ciao_certificate_samples): the call's own pass also keeps the row dots and a second reduction, over the N
+        samples, adds those terms: for logistic rows with NormL1(mu), mu > 0 the gap is F + g + E / N; the
+        other fields, and the lasso's gap, are bitwise what samples=False gives.  av / fval must then be None; not on a row-sharded
+        context."""
         from .certificate import assemble
         if isinstance(F, PackedSepQuad):
             raise L.CiaoError(L.ERR_ARG, "the certificate covers finite sums of LeastSquares / logistic rows, not the sharing problem")
+        if samples:
+            if av is not None or fval is not None:
+                raise L.CiaoError(L.ERR_ARG, "certificate(samples=True) makes its own pass (it needs the row dots): av= and fval= must be None")
+            return self.certificate_samples(F, g, x, gamma)[0]
         out = (C.c_double * 6)(float("nan") if fval is None else float(fval))
         L.check(self.lib.ciao_certificate(self._h, F.ref, g.ref if g is not None else None, self._vec(x, F, "x"),
                                           None if av is None else self._vec(av, F, "av"), float(gamma), out))
         mu = g.lam if (g is not None and F.loss == L.LOSS_LS and g.kind == L.PROX_L1) else None
         return assemble(*out, mu=mu)
+
+    def certificate_samples(self, F, g, x, gamma: float):
+        """certificate(samples=True) together with the per-sample statistics it rests on (include/ciao_hip.h:
+        ciao_certificate_samples) -> (certificate.CertificateResult, LogisticStats | LeastSquaresStats): the statistics are
+        margin_stats of the pass's own row dots at s = min(1, mu / grad_inf) for g = NormL1(mu), mu > 0 (s = 1 where grad f = 0 and
+        for every other g); synchronises."""
+        from .certificate import assemble
+        if isinstance(F, PackedSepQuad):
+            raise L.CiaoError(L.ERR_ARG, "the certificate covers finite sums of LeastSquares / logistic rows, not the sharing problem")
+        out = (C.c_double * 10)()
+        L.check(self.lib.ciao_certificate_samples(self._h, F.ref, g.ref if g is not None else None, self._vec(x, F, "x"), float(gamma), out))
+        l1 = g is not None and g.kind == L.PROX_L1
+        if F.loss == L.LOSS_LOGISTIC:
+            return assemble(*out[:6], mu=g.lam if l1 else None, entropy=out[7], n=F.N_total), LogisticStats(*out[6:])
+        return assemble(*out[:6], mu=g.lam if l1 else None), LeastSquaresStats(*out[6:])
+
+    def row_dots(self, F, x, out=None):
+        """out[i] = a_i'x for the N local rows of F (include/ciao_hip.h: ciao_row_dots) -> a device N-vector of F's dtype: the
+        per-sample predictions (LeastSquares) or scores (logistic: the margin is y_i a_i'x).  One full pass; does not synchronise."""
+        if isinstance(F, PackedSepQuad):
+            raise L.CiaoError(L.ERR_ARG, "row dots exist for LeastSquares / logistic rows, not for the sharing problem")
+        if out is None:
+            out = torch.empty(F.N, dtype=F.dtype, device=f"cuda:{self.device}")
+            if self.stream is not None:
+                out.record_stream(self.stream)
+        self._vec(out, F, "out", F.N)
+        L.check(self.lib.ciao_row_dots(self._h, F.ref, self._vec(x, F, "x"), _ptr(out) if F.N > 0 else None))
+        return out
+
+    def margin_stats(self, F, dots, s: float = 1.0):
+        """The per-sample reduction of `dots` (a device N-vector, e.g. row_dots(F, x)) against F's targets / labels
+        (include/ciao_hip.h: ciao_margin_stats) -> LogisticStats or LeastSquaresStats; synchronises."""
+        if isinstance(F, PackedSepQuad):
+            raise L.CiaoError(L.ERR_ARG, "margin statistics exist for LeastSquares / logistic rows, not for the sharing problem")
+        out = (C.c_double * 4)()
+        L.check(self.lib.ciao_margin_stats(self._h, F.ref, self._vec(dots, F, "dots", F.N), float(s), out))
+        return (LogisticStats if F.loss == L.LOSS_LOGISTIC else LeastSquaresStats)(*out)
 
     # -- SVRG ------------------------------------------------------------------------------------------------------------
     def svrg_init(self, p, x0, av, z, z_full, w):

@@ -337,9 +337,56 @@ def host_solution(state):
     return state.z_full if isinstance(state, HostSVRGState) else state.z
 
 
-def host_certificate(F, g, x, gamma, N):
+def _rows(F):
+    """("ls" | "logistic", A, b) in float64 when every f_i is a one-row LeastSquares / Precompose(LogisticLoss) term; else None."""
+    from . import operators as Op
+    if F and all(isinstance(f, Op.LeastSquares) and not np.iscomplexobj(f.A) for f in F):
+        return ("ls", np.concatenate([f.A for f in F], axis=0).astype(np.float64), np.concatenate([f.b for f in F]).astype(np.float64))
+    if F and all(isinstance(f, Op.Precompose) and isinstance(f.f, Op.LogisticLoss) and f.f.mu == 1.0 and not np.any(np.asarray(f.b) != 0) for f in F):
+        return ("logistic", np.concatenate([f.L for f in F], axis=0).astype(np.float64), np.concatenate([f.f.y for f in F]).astype(np.float64))
+    return None
+
+
+def host_margin_stats(kind, dots, b, s=1.0):
+    """The four numbers of ciao_margin_stats in numpy (float64), by the same stable evaluation (csrc/mstat_kernels.h)."""
+    dots, b = np.asarray(dots, np.float64), np.asarray(b, np.float64)
+    if kind == "ls":
+        r = dots - b
+        return float(np.sum(r * r)), float(np.sum(b)), float(np.sum(b * b)), float(np.max(np.abs(r)))
+    t = b * dots
+    e = np.exp(-np.abs(t))
+    big, small = 1.0 / (1.0 + e), e / (1.0 + e)
+    v = s * np.where(t >= 0, small, big)
+    w = (1.0 - s) + s * np.where(t >= 0, big, small)
+    xlogx = lambda u: np.where(u > 0, u * np.log(np.where(u > 0, u, 1.0)), 0.0)
+    return (float(np.sum(np.maximum(-t, 0.0) + np.log1p(e))), float(np.sum(xlogx(v) + xlogx(w))), float(np.sum(t <= 0)), float(np.min(t)))
+
+
+def _score(kind, stats, n):
+    """scoring.score's fields from the four statistics."""
+    from .scoring import LeastSquaresScore, LogisticScore
+    if kind == "ls":
+        sum_r2, sum_b, sum_b2, max_abs_r = stats
+        tss = sum_b2 - sum_b * sum_b / n
+        return LeastSquaresScore(sum_r2 / n, 1.0 - sum_r2 / tss if tss > 0 else float("nan"), max_abs_r)
+    loss_sum, _, errors, min_margin = stats
+    return LogisticScore(loss_sum / n, 1.0 - errors / n, min_margin)
+
+
+def host_score(F, x):
+    """scoring.score in numpy for operator objects (one-row LeastSquares or Precompose(LogisticLoss) terms): the same fields."""
+    x = np.asarray(x.detach().cpu() if hasattr(x, "detach") else x).reshape(-1).astype(np.float64)
+    rows = _rows(list(F))
+    if rows is None:
+        raise TypeError("host_score needs F as one-row LeastSquares terms or Precompose(LogisticLoss) terms")
+    kind, A, b = rows
+    return _score(kind, host_margin_stats(kind, A @ x, b, 1.0), len(b))
+
+
+def host_certificate(F, g, x, gamma, N, samples=False):
     """certificate.CertificateResult at x in numpy (float64): the quantities of ciao_certificate for operator objects -- the host
-    route's answer to certificate.Certificate.  The gap applies when every f_i is a LeastSquares and g = NormL1(mu), mu > 0."""
+    route's answer to certificate.Certificate.  The gap applies when every f_i is a LeastSquares and g = NormL1(mu), mu > 0; with
+    samples=True also when every f_i is a Precompose(LogisticLoss) row (the per-sample entropy, as ciao_certificate_samples)."""
     from . import operators as Op
     from .certificate import assemble
     x = np.asarray(x.detach().cpu() if hasattr(x, "detach") else x).reshape(-1).astype(np.float64)
@@ -355,6 +402,14 @@ def host_certificate(F, g, x, gamma, N):
     if isinstance(g, Op.IndBox):
         lo, hi = np.asarray(g.lo, dtype=np.float64), np.asarray(g.hi, dtype=np.float64)
         viol = float(max(np.max(lo - x), np.max(x - hi), 0.0))
+    rows = _rows(F) if (samples and isinstance(g, Op.NormL1)) else None
+    if rows is not None and rows[0] == "logistic":
+        grad_inf = float(np.max(np.abs(av))) if x.size else 0.0
+        mu = float(g.lam)
+        s = 1.0 if (grad_inf == 0 or mu <= 0) else min(1.0, mu / grad_inf)
+        entropy = host_margin_stats("logistic", rows[1] @ x, rows[2], s)[1]
+        return assemble(fsum / len(F), _gval(g, x), float(np.linalg.norm(r)) / gamma, grad_inf, float(x @ av), viol, mu=mu, entropy=entropy,
+                        n=len(F))
     lasso = isinstance(g, Op.NormL1) and len(F) > 0 and all(isinstance(f, Op.LeastSquares) for f in F)
     return assemble(fsum / max(len(F), 1), _gval(g, x), float(np.linalg.norm(r)) / gamma, float(np.max(np.abs(av))) if x.size else 0.0,
                     float(x @ av), viol, mu=float(g.lam) if lasso else None)

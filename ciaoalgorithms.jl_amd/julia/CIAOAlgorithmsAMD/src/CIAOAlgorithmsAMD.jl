@@ -331,6 +331,45 @@ function certificate(F::PackedF{R}, g::CiaoProxDesc, x::ROCArray{R,1}, γ::Real;
             box_violation = viol, gap = gap)
 end
 
+# The per-sample side (include/ciao_hip.h: ciao_row_dots, ciao_margin_stats, ciao_certificate_samples; Python twins:
+# device.Context.row_dots / margin_stats / certificate(samples = true), scoring.py).  row_dots: a_i'x for every local row, on the
+# device -- the predictions of a fitted model.  margin_stats: their reduction against b; logistic rows (t_i = y_i a_i'x):
+# (Σ log(1+exp(−t_i)), E(s) = Σ h(s σ(−t_i)), #{t_i ≤ 0}, min t_i); LeastSquares rows (r_i = a_i'x − b_i): (Σ r_i², Σ b_i, Σ b_i², max |r_i|).
+function row_dots(F::PackedF{R}, x::ROCArray{R,1}; out::ROCArray{R,1} = ROCArray{R}(undef, Int(F.N))) where {R}
+    check(ccall((:ciao_row_dots, libciao), Int32, (Ptr{Cvoid}, Ref{CiaoProblem}, Ptr{Cvoid}, Ptr{Cvoid}),
+                context().h, Ref(cproblem(F)), dptr(x), dptr(out)))
+    return out
+end
+
+function margin_stats(F::PackedF{R}, dots::ROCArray{R,1}; s::Real = 1.0) where {R}
+    out = zeros(Float64, 4)
+    check(ccall((:ciao_margin_stats, libciao), Int32, (Ptr{Cvoid}, Ref{CiaoProblem}, Ptr{Cvoid}, Float64, Ptr{Float64}),
+                context().h, Ref(cproblem(F)), dptr(dots), Float64(s), out))
+    return out
+end
+
+# certificate(...) with the per-sample terms: the same eight fields, and for logistic rows with g = NormL1(μ), μ > 0 the duality gap
+# F + g + E(s)/N at the dual point u_i = s σ(−t_i), s = min(1, μ/‖∇f‖∞) formed on the device (DESIGN.md section 8.7).  `stats`: the
+# four numbers of margin_stats on the pass's own row dots.  Not on a row-sharded context.
+function certificate_samples(F::PackedF{R}, g::CiaoProxDesc, x::ROCArray{R,1}, γ::Real) where {R}
+    out = zeros(Float64, 10)
+    check(ccall((:ciao_certificate_samples, libciao), Int32, (Ptr{Cvoid}, Ref{CiaoProblem}, Ref{CiaoProxDesc}, Ptr{Cvoid}, Float64, Ptr{Float64}),
+                context().h, Ref(cproblem(F)), Ref(g), dptr(x), Float64(γ), out))
+    Fv, gv, residual, grad_inf, x_dot_grad, viol = out[1:6]
+    gval = viol > 0 ? Inf : gv
+    gap = NaN
+    if g.kind == PROX_L1 && g.lam > 0
+        if F.loss == LOSS_LOGISTIC
+            gap = Fv + gval + out[8] / F.N
+        elseif F.loss == LOSS_LS
+            s = grad_inf == 0 ? 1.0 : min(1.0, g.lam / grad_inf)
+            gap = Fv + gval - (Fv * (2s - s^2) - s * x_dot_grad)
+        end
+    end
+    return (F = Fv, g = gval, objective = Fv + gval, residual = residual, grad_inf = grad_inf, x_dot_grad = x_dot_grad,
+            box_violation = viol, gap = gap, stats = out[7:10])
+end
+
 # ======================================================================================================================
 # SVRG  (src/algorithms/SVRG/SVRG.jl, SVRG_basic.jl)
 # ======================================================================================================================

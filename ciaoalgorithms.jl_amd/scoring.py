@@ -1,0 +1,30 @@
+"""Scores of a fitted model on device rows: predictions never leave the GPU.
+
+    score(ctx, F, x)    F: device.PackedF -- the training rows, or NEW rows with the same d (the prediction path)
+
+One full pass gives the row dots a_i'x (Context.row_dots), one reduction over the N samples the sums (Context.margin_stats, s = 1);
+the fields below are formed from those four doubles on the host.  For operator objects on the host route: host_route.host_score.
+"""
+from __future__ import annotations
+
+from typing import NamedTuple
+
+
+class LeastSquaresScore(NamedTuple):
+    mse: float                # (1/N) sum_i (a_i'x - b_i)^2
+    r2: float                 # 1 - sum_i (a_i'x - b_i)^2 / sum_i (b_i - mean b)^2   (nan where b is constant)
+    max_abs_residual: float   # max_i |a_i'x - b_i|
+
+
+class LogisticScore(NamedTuple):
+    log_loss: float           # (1/N) sum_i log(1 + exp(-y_i a_i'x))
+    accuracy: float           # 1 - #{i: y_i a_i'x <= 0} / N
+    min_margin: float         # min_i y_i a_i'x
+
+
+def score(ctx, F, x):
+    """LeastSquaresScore or LogisticScore of x on the rows of F (a device.PackedF of LeastSquares or logistic rows); synchronises."""
+    from . import _lib as L
+    from .host_route import _score
+    stats = ctx.margin_stats(F, ctx.row_dots(F, x), 1.0)
+    return _score("logistic" if F.loss == L.LOSS_LOGISTIC else "ls", tuple(stats), F.N)

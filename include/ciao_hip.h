@@ -205,6 +205,25 @@ CIAO_API int32_t ciao_objective(ciao_ctx *ctx, const ciao_problem *p, const ciao
  * The five reductions are bitwise reproducible: their order is a function of d alone.  Synchronises. */
 CIAO_API int32_t ciao_certificate(ciao_ctx *ctx, const ciao_problem *p, const ciao_prox_desc *g, const void *x,
                                   const void *av, double gamma, double *out_host);
+/* Row dots: out[i] = a_i'x for the N local rows (device memory, N elements of T) -- the predictions of a fitted model, per sample.
+ * Not in the reference (its f_i are one-row operator objects; test/test_logistic_l1.jl forms A*x on the host).  One full pass, the
+ * certificate's own; grad f(x) goes to the context's workspace.  Real T with data rows only (CIAO_LOSS_ZERO and complex problems are
+ * refused).  On a row-sharded context: the local rows.  Does not synchronise. */
+CIAO_API int32_t ciao_row_dots(ciao_ctx *ctx, const ciao_problem *p, const void *x, void *out);
+/* Per-sample statistics of given row dots (device memory, N of T) against p->b, reduced on the device.  Logistic rows, t_i = b_i dots_i:
+ * out_host[0] = sum_i log(1 + exp(-t_i)), [1] = E(s) = sum_i h(s sigma(-t_i)) with h(u) = u log u + (1-u) log(1-u) (the entropy of the
+ * logistic dual at the point scaled by s), [2] = the number of samples with t_i <= 0 (misclassified), [3] = min_i t_i.  LeastSquares
+ * rows, r_i = dots_i - b_i: [0] = sum_i r_i^2, [1] = sum_i b_i, [2] = sum_i b_i^2, [3] = max_i |r_i|.  Serves log-loss / accuracy /
+ * RMSE / R^2 of a fitted model (the reference's tests compute them outside) and the logistic duality gap.  0 <= s <= 1; N >= 1; real
+ * T with data rows only.  Bitwise reproducible: the order of every sum is a function of N alone.  Synchronises. */
+CIAO_API int32_t ciao_margin_stats(ciao_ctx *ctx, const ciao_problem *p, const void *dots, double s, double *out_host);
+/* ciao_certificate with its per-sample terms.  out_host[0..5] are exactly ciao_certificate's six numbers (av = NULL: the call makes
+ * its pass), [6..9] the four numbers of ciao_margin_stats on that pass's row dots with s = min(1, mu / ||grad f(x)||_inf) formed on
+ * the device (mu = g->lam for CIAO_PROX_L1 with lam > 0; s = 1 otherwise, and where grad f(x) = 0).  For logistic rows and NormL1
+ * the duality gap is out[0] + out[1] + out[7] / N (no counterpart in the reference: `stop(state) = false`, SVRG.jl:55).  Refused on a
+ * row-sharded context (all-reduce hook or shard table set), for N = 0, CIAO_LOSS_ZERO and complex problems.  Synchronises. */
+CIAO_API int32_t ciao_certificate_samples(ciao_ctx *ctx, const ciao_problem *p, const ciao_prox_desc *g, const void *x,
+                                          double gamma, double *out_host);
 
 /* ---- SVRG / SVRG++  (SVRG/SVRG_basic.jl) -------------------------------------------------------------------- */
 /* Base.iterate(iter), :57-66: av = full gradient at x0; z_full = x0; z = 0; w = x0. */
