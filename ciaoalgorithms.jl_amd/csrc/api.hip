@@ -989,6 +989,21 @@ static int32_t certificate_samples_t(ciao_ctx *ctx, const ciao_problem *p, const
     return CIAO_OK;
 }
 
+// the screening rule over d coordinates: two kernels, one copy of the count, one synchronisation
+template <typename T>
+static int32_t screen_t(ciao_ctx *ctx, int64_t d, const void *grad, const double *colsq, double s, double kappa, double mu, uint8_t *keep,
+                        int64_t *n_kept_host)
+{
+    CIAO_TRY(ensure(ctx, &ctx->cert, &ctx->cert_bytes, (size_t)SCREEN_WS_DOUBLES * sizeof(double)));
+    double *res = (double *)ctx->cert;
+    CIAO_TRY(launch_screen<T>(ctx, d, grad, colsq, s, kappa, mu, keep, res + 8, res));
+    double cnt = 0.0;
+    CIAO_HIP(hipMemcpyAsync(&cnt, res, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream));
+    CIAO_HIP(hipStreamSynchronize(ctx->stream));
+    *n_kept_host = (int64_t)cnt;
+    return CIAO_OK;
+}
+
 }  // namespace ciao
 
 using namespace ciao;
@@ -1662,6 +1677,30 @@ int32_t ciao_certificate_samples(ciao_ctx *ctx, const ciao_problem *p, const cia
     CIAO_REQUIRE(x && out_host, "x or out_host is NULL");
     CIAO_REQUIRE(gamma > 0 && gamma <= 1.79769313486231570815e308, "gamma must be > 0 and finite");
     return DISPATCH(p->dtype, certificate_samples_t, ctx, p, g, x, gamma, out_host);
+}
+
+int32_t ciao_col_sqnorms(ciao_ctx *ctx, const ciao_problem *p, double *out)
+{
+    CIAO_REQUIRE(ctx && p && out, "ciao_col_sqnorms: the context, the problem or the output vector is NULL");
+    CIAO_ENTER(ctx);
+    CIAO_TRY(check_problem(ctx, p));
+    CIAO_REQUIRE(p->loss != CIAO_LOSS_LS_COMPLEX, "ciao_col_sqnorms covers real problems only (complex T: screening is not defined on (re, im) pairs)");
+    CIAO_REQUIRE(p->loss != CIAO_LOSS_ZERO, "ciao_col_sqnorms needs data rows (Zero() terms have no matrix A)");
+    CIAO_REQUIRE(p->N >= 1, "ciao_col_sqnorms needs at least one resident row (N = 0: there are no columns to sum)");
+    return p->dtype == CIAO_F64 ? launch_colsq<double>(ctx, p, out) : launch_colsq<float>(ctx, p, out);
+}
+
+int32_t ciao_screen(ciao_ctx *ctx, int32_t dtype, int64_t d, const void *grad, const double *colsq, double s, double kappa, double mu,
+                    uint8_t *keep, int64_t *n_kept_host)
+{
+    CIAO_REQUIRE(ctx && grad && colsq && keep && n_kept_host, "ciao_screen: the context, grad, colsq, keep or n_kept_host is NULL");
+    CIAO_ENTER(ctx);
+    CIAO_REQUIRE(dtype == CIAO_F32 || dtype == CIAO_F64, "ciao_screen: dtype must be CIAO_F32 or CIAO_F64 (got %d)", dtype);
+    CIAO_REQUIRE(d >= 1, "ciao_screen needs at least one coordinate (got d = %lld)", (long long)d);
+    CIAO_REQUIRE(s >= 0.0 && s <= 1.0, "ciao_screen: the dual scaling s must lie in [0, 1] (got %g)", s);
+    CIAO_REQUIRE(kappa >= 0.0, "ciao_screen: the radius kappa must be >= 0 and not NaN (got %g; +inf keeps every coordinate)", kappa);
+    CIAO_REQUIRE(mu > 0.0 && mu <= 1.79769313486231570815e308, "ciao_screen: the l1 weight mu must be > 0 and finite (got %g)", mu);
+    return DISPATCH(dtype, screen_t, ctx, d, grad, colsq, s, kappa, mu, keep, n_kept_host);
 }
 
 int32_t ciao_svrg_init(ciao_ctx *ctx, const ciao_problem *p, const void *x0, void *av, void *z, void *z_full, void *w)

@@ -138,6 +138,17 @@ template <typename T>
 int32_t launch_mstat(ciao_ctx *ctx, int loss, int64_t N, const void *dots, const void *b, double s, const double *M_dev, double mu,
                      double *rec, double *out);
 
+// Gap-safe screening (colsq_kernels.h).  launch_colsq: out[j] = sum_i A[i,j]^2 over the N local rows, d device doubles; the partial
+// d-vectors go to ctx->partial (grown here).  launch_screen: keep[k] = !(s |grad_k| + kappa sqrt(colsq_k) < mu) and their count into
+// *cnt (device); rec = workspace of CERT_GRID_CAP records.  Workspace of ciao_screen (ctx->cert): [0] the count, [8..) the records.
+// Specialised in colsq_f32.hip / colsq_f64.hip.
+constexpr int SCREEN_WS_DOUBLES = 8 + 512 * 8;
+template <typename T>
+int32_t launch_colsq(ciao_ctx *ctx, const ciao_problem *p, double *out);
+template <typename T>
+int32_t launch_screen(ciao_ctx *ctx, int64_t d, const void *grad, const double *colsq, double s, double kappa, double mu, uint8_t *keep,
+                      double *rec, double *cnt);
+
 // ProShI agent rows (init or one batch) + finalize + epilogue.  Specialised in rows_f32.hip / rows_f64.hip.
 template <typename T>
 int32_t launch_proshi(ciao_ctx *ctx, bool init, ProshiArgs<T> &a, const Epilogue<T> &ep);

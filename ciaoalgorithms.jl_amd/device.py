@@ -233,6 +233,8 @@ class Context:
         handle = C.c_void_p(stream.cuda_stream) if stream is not None else None
         L.check(self.lib.ciao_ctx_create(self.device, handle, C.byref(self._h)))
         self._hook_keepalive = None
+        self._rccl_keepalive = None
+        self._peers_keepalive = None
         self._batch_keep = None        # index tensors of an open chain batch (kept alive until its launch is enqueued)
         self.shards = None
 
@@ -328,6 +330,12 @@ class Context:
         self._rccl_keepalive = comm
         self._hook_keepalive = None
         L.check(self.lib.ciao_ctx_set_rccl(self._h, comm.handle, comm.lib_path.encode()))
+
+    def is_row_sharded(self) -> bool:
+        """True while this context sums over other ranks' rows: an all-reduce hook (set_allreduce), an RCCL communicator (set_rccl),
+        a shard table (set_shards) or peer mailboxes (set_peers) is set."""
+        return (self._hook_keepalive is not None or self._rccl_keepalive is not None or self.shards is not None
+                or self._peers_keepalive is not None)
 
     # -- helpers -------------------------------------------------------------------------------------------------------
     def _vec(self, t: torch.Tensor, p: PackedF, name: str, n: int | None = None):
@@ -449,6 +457,39 @@ class Context:
         out = (C.c_double * 4)()
         L.check(self.lib.ciao_margin_stats(self._h, F.ref, self._vec(dots, F, "dots", F.N), float(s), out))
         return (LogisticStats if F.loss == L.LOSS_LOGISTIC else LeastSquaresStats)(*out)
+
+    # -- gap-safe screening (screening.py) ----------------------------------------------------------
+    def col_sqnorms(self, F, out=None):
+        """out[j] = sum_i A[i,j]^2 over the N local rows of F (include/ciao_hip.h: ciao_col_sqnorms) -> a device float64 d-vector
+        whatever F's dtype is.  One pass over A, paid once per dataset; bitwise reproducible.  Does not synchronise, except where the
+        workspace of partial sums has to grow (the first call at a larger N x d)."""
+        if isinstance(F, PackedSepQuad):
+            raise L.CiaoError(L.ERR_ARG, "column norms exist for LeastSquares / logistic rows, not for the sharing problem")
+        if out is None:
+            out = torch.empty(F.d, dtype=torch.float64, device=f"cuda:{self.device}")
+            if self.stream is not None:
+                out.record_stream(self.stream)
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == F.d):
+            raise ValueError(f"out: need a contiguous float64 device vector of length {F.d}")
+        L.check(self.lib.ciao_col_sqnorms(self._h, F.ref, _ptr(out)))
+        return out
+
+    def screen(self, grad, colsq, s: float, kappa: float, mu: float):
+        """The screening rule keep[j] = !(s |grad_j| + kappa sqrt(colsq_j) < mu) on the device (include/ciao_hip.h: ciao_screen) ->
+        (keep, n_kept): keep a uint8 device d-vector, n_kept the number of ones.  grad: a float32 / float64 device d-vector;
+        colsq: col_sqnorms' float64 d-vector.  Synchronises."""
+        if not (isinstance(grad, torch.Tensor) and grad.is_cuda and grad.dtype in _DT and grad.is_contiguous() and grad.dim() == 1):
+            raise ValueError("grad: need a contiguous float32 / float64 device vector")
+        d = grad.numel()
+        if not (isinstance(colsq, torch.Tensor) and colsq.is_cuda and colsq.dtype == torch.float64 and colsq.is_contiguous() and colsq.numel() == d):
+            raise ValueError(f"colsq: need a contiguous float64 device vector of length {d} (Context.col_sqnorms)")
+        keep = torch.empty(d, dtype=torch.uint8, device=grad.device)
+        if self.stream is not None:
+            keep.record_stream(self.stream)
+        n = C.c_int64(-1)
+        L.check(self.lib.ciao_screen(self._h, _DT[grad.dtype], d, _ptr(grad) if d else None, _ptr(colsq) if d else None, float(s), float(kappa),
+                                     float(mu), _ptr(keep) if d else None, C.byref(n)))
+        return keep, n.value
 
     # -- SVRG ------------------------------------------------------------------------------------------------------------
     def svrg_init(self, p, x0, av, z, z_full, w):

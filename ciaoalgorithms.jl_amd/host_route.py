@@ -415,6 +415,17 @@ def host_certificate(F, g, x, gamma, N, samples=False):
                     float(x @ av), viol, mu=float(g.lam) if lasso else None)
 
 
+def host_screen(grad, colsq, s, kappa, mu):
+    """The gap-safe screening rule of ciao_screen in numpy (float64): keep[j] = not (s |grad_j| + kappa sqrt(colsq_j) < mu), a boolean
+    d-vector; a NaN anywhere keeps the coordinate.  The same operations in the same order as csrc/colsq_kernels.h: screen_kernel (numpy
+    contracts nothing either), so the two masks differ only where the left side is within rounding of mu (a device sqrt or a
+    float32 -> float64 conversion cannot differ: both are exact / correctly rounded)."""
+    g = np.abs(np.asarray(grad).astype(np.float64))
+    with np.errstate(invalid="ignore"):
+        lhs = float(s) * g + float(kappa) * np.sqrt(np.asarray(colsq, dtype=np.float64))
+        return ~(lhs < float(mu))
+
+
 def announce(why):
     warnings.warn("CIAOAlgorithms (AMD): this problem runs on the HOST route -- numpy, one operator call per sample, no GPU -- "
                   f"because {why}.  It is orders of magnitude slower than the device path and none of this package's "

@@ -370,6 +370,43 @@ function certificate_samples(F::PackedF{R}, g::CiaoProxDesc, x::ROCArray{R,1}, Î
             box_violation = viol, gap = gap, stats = out[7:10])
 end
 
+# Gap-safe feature screening (include/ciao_hip.h: ciao_col_sqnorms, ciao_screen; Python twins: device.Context.col_sqnorms / screen,
+# screening.gap_safe; DESIGN.md section 8.8).  col_sqnorms: Î£_i A[i,j]Â² per column, Float64 whatever R is -- one pass over A, once per
+# dataset.  screen: keep[j] = !(s|âˆ‡f_j| + Îºâˆšcolsq_j < Î¼), one byte per coordinate, and the number kept.
+function col_sqnorms(F::PackedF{R}; out::ROCArray{Float64,1} = ROCArray{Float64}(undef, Int(F.d))) where {R}
+    check(ccall((:ciao_col_sqnorms, libciao), Int32, (Ptr{Cvoid}, Ref{CiaoProblem}, Ptr{Cvoid}),
+                context().h, Ref(cproblem(F)), dptr(out)))
+    return out
+end
+
+function screen(grad::ROCArray{R,1}, colsq::ROCArray{Float64,1}, s::Real, Îº::Real, Î¼::Real) where {R}
+    keep = ROCArray{UInt8}(undef, length(grad))
+    n_kept = Ref{Int64}(0)
+    check(ccall((:ciao_screen, libciao), Int32,
+                (Ptr{Cvoid}, Int32, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Ptr{Cvoid}, Ref{Int64}),
+                context().h, R === Float64 ? Int32(1) : Int32(0), Int64(length(grad)), dptr(grad), dptr(colsq), Float64(s), Float64(Îº), Float64(Î¼),
+                dptr(keep), n_kept))
+    return keep, n_kept[]
+end
+
+# Screen at x for g = NormL1(Î¼), Î¼ > 0, on LeastSquares or logistic rows (single device): two passes over A (âˆ‡f(x); the certificate,
+# with its per-sample terms for logistic rows) plus the column pass unless `colsq` is cached.  s = min(1, Î¼/â€–âˆ‡fâ€–âˆž) (1 where âˆ‡f = 0) is
+# the certificate's dual scaling; G = max(gap, 0) + 64 eps(R) objective (the floor: at a computed gap of 0 the support sits on
+# |âˆ‡f_j| = Î¼ to rounding); Îº = âˆš(2 Î» G / N) for LeastSquares(Î») rows, âˆš(G / 2N) for logistic rows; gap NaN or Inf: Îº = Inf, all kept.
+function gap_safe(F::PackedF{R}, g::CiaoProxDesc, x::ROCArray{R,1}, Î³::Real; colsq = nothing) where {R}
+    (g.kind == PROX_L1 && g.lam > 0 && (F.loss == LOSS_LS || F.loss == LOSS_LOGISTIC)) ||
+        throw(ArgumentError("gap_safe needs g = NormL1(Î¼), Î¼ > 0 and LeastSquares or logistic rows"))
+    grad = ROCArray{R}(undef, Int(F.d))
+    full_gradient!(grad, F, x)
+    cert = F.loss == LOSS_LOGISTIC ? certificate_samples(F, g, x, Î³) : certificate(F, g, x, Î³)
+    s = cert.grad_inf == 0 ? 1.0 : min(1.0, g.lam / cert.grad_inf)
+    G = isnan(cert.gap) ? NaN : max(cert.gap, 0.0) + 64 * Float64(eps(R)) * cert.objective
+    Îº = !(G < Inf) ? Inf : F.loss == LOSS_LS ? sqrt(2 * F.lam * max(G, 0.0) / F.N) : sqrt(max(G, 0.0) / (2 * F.N))
+    cs = colsq === nothing ? col_sqnorms(F) : colsq
+    keep, n_kept = screen(grad, cs, s, Îº, g.lam)
+    return (keep = keep, n_kept = n_kept, d = Int(F.d), s = s, kappa = Îº, certificate = cert)
+end
+
 # ======================================================================================================================
 # SVRG  (src/algorithms/SVRG/SVRG.jl, SVRG_basic.jl)
 # ======================================================================================================================

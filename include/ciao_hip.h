@@ -224,6 +224,24 @@ CIAO_API int32_t ciao_margin_stats(ciao_ctx *ctx, const ciao_problem *p, const v
  * row-sharded context (all-reduce hook or shard table set), for N = 0, CIAO_LOSS_ZERO and complex problems.  Synchronises. */
 CIAO_API int32_t ciao_certificate_samples(ciao_ctx *ctx, const ciao_problem *p, const ciao_prox_desc *g, const void *x,
                                           double gamma, double *out_host);
+/* EXTENSION beyond the reference (as ciao_full_gradient_multi is): gap-safe feature screening for l1 problems.  The reference has
+ * no screening and no duality gap (`stop(state) = false`, SVRG.jl:55); DESIGN.md section 8.8 has the rule and its radii.
+ * Column sums of squares: out[j] = sum_i A[i,j]^2 for j < d over the N resident rows; out is a device vector of d DOUBLES whatever
+ * p->dtype is.  One pass over A (every element read once, squares formed and added in double), no atomics: bitwise reproducible
+ * between runs, contexts, row strides and pointer alignments -- every order of addition is a function of (N, d) alone.  Real
+ * CIAO_LOSS_LS / CIAO_LOSS_LOGISTIC problems; complex problems, CIAO_LOSS_ZERO (no A), N = 0 and NULL arguments are refused with
+ * CIAO_ERR_ARG and nothing is launched.  On a row-sharded context: the LOCAL rows only, as ciao_row_dots (the caller sums the
+ * ranks' vectors).  Workspace: at most 32 MiB of partial sums (8 d bytes where that is more).  Does not synchronise,
+ * except where that workspace has to grow (the first call at a larger N x d waits for the stream and reallocates). */
+CIAO_API int32_t ciao_col_sqnorms(ciao_ctx *ctx, const ciao_problem *p, double *out);
+/* EXTENSION beyond the reference: the screening rule.  grad = grad f(x), a device d-vector of dtype; colsq = what ciao_col_sqnorms
+ * wrote (device, d doubles); keep = d device bytes.  Per coordinate, in double, without contraction:
+ *     keep[j] = !( s |grad_j| + kappa sqrt(colsq_j) < mu )
+ * so that a NaN anywhere keeps the coordinate; *n_kept_host = the number of kept coordinates.  With s and kappa from the duality
+ * gap every dropped coordinate is zero at the optimum.  0 <= s <= 1; kappa >= 0 (+inf allowed: keeps
+ * everything; NaN refused); mu > 0 and finite; d >= 1; no NULL argument: otherwise CIAO_ERR_ARG.  Synchronises. */
+CIAO_API int32_t ciao_screen(ciao_ctx *ctx, int32_t dtype, int64_t d, const void *grad, const double *colsq, double s, double kappa,
+                             double mu, uint8_t *keep, int64_t *n_kept_host);
 
 /* ---- SVRG / SVRG++  (SVRG/SVRG_basic.jl) -------------------------------------------------------------------- */
 /* Base.iterate(iter), :57-66: av = full gradient at x0; z_full = x0; z = 0; w = x0. */
