@@ -1004,6 +1004,20 @@ static int32_t screen_t(ciao_ctx *ctx, int64_t d, const void *grad, const double
     return CIAO_OK;
 }
 
+// the row sums of squares: one kernel (two with the summary); with stats_host one copy of four doubles and one synchronisation
+template <typename T>
+static int32_t row_sqnorms_t(ciao_ctx *ctx, const ciao_problem *p, double *out, double *stats_host)
+{
+    CIAO_TRY(ensure(ctx, &ctx->cert, &ctx->cert_bytes, (size_t)ROWSQ_WS_DOUBLES * sizeof(double)));
+    double *res = (double *)ctx->cert;
+    CIAO_TRY(launch_rowsq<T>(ctx, p, out, res + 8, stats_host ? res : nullptr));
+    if (stats_host) {
+        CIAO_HIP(hipMemcpyAsync(stats_host, res, 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        CIAO_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return CIAO_OK;
+}
+
 }  // namespace ciao
 
 using namespace ciao;
@@ -1688,6 +1702,17 @@ int32_t ciao_col_sqnorms(ciao_ctx *ctx, const ciao_problem *p, double *out)
     CIAO_REQUIRE(p->loss != CIAO_LOSS_ZERO, "ciao_col_sqnorms needs data rows (Zero() terms have no matrix A)");
     CIAO_REQUIRE(p->N >= 1, "ciao_col_sqnorms needs at least one resident row (N = 0: there are no columns to sum)");
     return p->dtype == CIAO_F64 ? launch_colsq<double>(ctx, p, out) : launch_colsq<float>(ctx, p, out);
+}
+
+int32_t ciao_row_sqnorms(ciao_ctx *ctx, const ciao_problem *p, double *out, double *stats_host)
+{
+    CIAO_REQUIRE(ctx && p, "ciao_row_sqnorms: the context or the problem is NULL");
+    CIAO_ENTER(ctx);
+    CIAO_TRY(check_problem(ctx, p));
+    CIAO_REQUIRE(p->loss != CIAO_LOSS_ZERO, "ciao_row_sqnorms needs data rows (Zero() terms have no matrix A)");
+    CIAO_REQUIRE(p->N >= 1, "ciao_row_sqnorms needs at least one resident row (N = 0: there is no row to sum)");
+    CIAO_REQUIRE(out || stats_host, "ciao_row_sqnorms: out and stats_host are both NULL (nothing was asked for)");
+    return DISPATCH(p->dtype, row_sqnorms_t, ctx, p, out, stats_host);
 }
 
 int32_t ciao_screen(ciao_ctx *ctx, int32_t dtype, int64_t d, const void *grad, const double *colsq, double s, double kappa, double mu,

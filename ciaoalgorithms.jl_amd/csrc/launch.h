@@ -149,6 +149,14 @@ template <typename T>
 int32_t launch_screen(ciao_ctx *ctx, int64_t d, const void *grad, const double *colsq, double s, double kappa, double mu, uint8_t *keep,
                       double *rec, double *cnt);
 
+// Row sums of squares and their summary (rowsq_kernels.h).  launch_rowsq: out[i] = sum_j A[i,j]^2 for the N local rows (N device doubles,
+// or NULL), one record per workgroup into rec (ROWSQ_WG_TARGET records at most) and, where res is non-NULL, {max, argmax, min, sum} into
+// res[0..4) (device).  Workspace of ciao_row_sqnorms (ctx->cert): [0..8) the summary, [8..) the records.  Specialised in rowsq_f32.hip /
+// rowsq_f64.hip.
+constexpr int ROWSQ_WS_DOUBLES = 8 + 2048 * 8;
+template <typename T>
+int32_t launch_rowsq(ciao_ctx *ctx, const ciao_problem *p, double *out, double *rec, double *res);
+
 // ProShI agent rows (init or one batch) + finalize + epilogue.  Specialised in rows_f32.hip / rows_f64.hip.
 template <typename T>
 int32_t launch_proshi(ciao_ctx *ctx, bool init, ProshiArgs<T> &a, const Epilogue<T> &ep);

@@ -198,6 +198,14 @@ class LeastSquaresStats(NamedTuple):
     max_abs_r: float    # max_i |r_i|
 
 
+class RowNormStats(NamedTuple):
+    """Context.row_sqnorm_stats: the summary of the row sums of squares ||a_i||^2 over the N local rows."""
+    max: float          # max_i ||a_i||^2 (NaN where any row holds a NaN)
+    argmax: int         # the smallest row index that attains it
+    min: float          # min_i ||a_i||^2
+    sum: float          # sum_i ||a_i||^2 = ||A||_F^2 = trace(A'A)
+
+
 class _ChainBatch:
     """Context manager of Context.chain_batch()."""
 
@@ -490,6 +498,33 @@ class Context:
         L.check(self.lib.ciao_screen(self._h, _DT[grad.dtype], d, _ptr(grad) if d else None, _ptr(colsq) if d else None, float(s), float(kappa),
                                      float(mu), _ptr(keep) if d else None, C.byref(n)))
         return keep, n.value
+
+    # -- step sizes from the data (stepsize.py) ---------------------------------------------------------
+    def _row_sqnorms(self, F, out, stats):
+        if isinstance(F, PackedSepQuad):
+            raise L.CiaoError(L.ERR_ARG, "row norms exist for LeastSquares / logistic rows, not for the sharing problem")
+        L.check(self.lib.ciao_row_sqnorms(self._h, F.ref, _ptr(out), stats))
+
+    def row_sqnorms(self, F, out=None):
+        """out[i] = sum_j A[i,j]^2 = ||a_i||^2 for the N local rows of F (include/ciao_hip.h: ciao_row_sqnorms) -> a device float64
+        N-vector whatever F's dtype is (a complex row: the sum over its 2n reals).  One pass over A; bitwise reproducible.  Does not
+        synchronise."""
+        if out is None and not isinstance(F, PackedSepQuad):
+            out = torch.empty(F.N, dtype=torch.float64, device=f"cuda:{self.device}")
+            if self.stream is not None:
+                out.record_stream(self.stream)
+        if not isinstance(F, PackedSepQuad) and not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64
+                                                     and out.is_contiguous() and out.numel() == F.N):
+            raise ValueError(f"out: need a contiguous float64 device vector of length {F.N}")
+        self._row_sqnorms(F, out, None)
+        return out
+
+    def row_sqnorm_stats(self, F) -> RowNormStats:
+        """The summary of row_sqnorms(F) without its N-vector: RowNormStats(max, argmax, min, sum) from the same pass over A (no
+        N-vector is allocated or written).  Bitwise the numbers row_sqnorms' vector has; synchronises."""
+        stats = (C.c_double * 4)()
+        self._row_sqnorms(F, None, stats)
+        return RowNormStats(stats[0], int(stats[1]), stats[2], stats[3])
 
     # -- SVRG ------------------------------------------------------------------------------------------------------------
     def svrg_init(self, p, x0, av, z, z_full, w):

@@ -426,6 +426,25 @@ def host_screen(grad, colsq, s, kappa, mu):
         return ~(lhs < float(mu))
 
 
+def host_row_sqnorms(A):
+    """The row sums of squares of ciao_row_sqnorms in numpy (float64): out[i] = sum_j |A[i,j]|^2, a complex row as its 2n reals.  The
+    squares are what the device forms ((double)a * (double)a); the order of addition is numpy's, so the two agree to
+    (d + 2) 2^-53 relative, not bitwise."""
+    A = np.asarray(A)
+    if np.iscomplexobj(A):
+        A = np.ascontiguousarray(A).view(A.real.dtype).reshape(A.shape[0], -1)
+    A = A.astype(np.float64)
+    return np.sum(A * A, axis=1)
+
+
+def host_lipschitz(kind, A, lam=1.0):
+    """The per-sample smoothness constants of stepsize.lipschitz in numpy (float64): lam ||a_i||^2 for LeastSquares(a_i, b_i, lam) rows
+    (kind "ls", real or complex; test_lasso.jl:52-56), ||a_i||^2 / 4 for logistic rows (kind "logistic"; test_logistic_l1.jl:39)."""
+    if kind not in ("ls", "logistic"):
+        raise ValueError(f"kind must be 'ls' or 'logistic' (got {kind!r})")
+    return (float(lam) if kind == "ls" else 0.25) * host_row_sqnorms(A)
+
+
 def announce(why):
     warnings.warn("CIAOAlgorithms (AMD): this problem runs on the HOST route -- numpy, one operator call per sample, no GPU -- "
                   f"because {why}.  It is orders of magnitude slower than the device path and none of this package's "

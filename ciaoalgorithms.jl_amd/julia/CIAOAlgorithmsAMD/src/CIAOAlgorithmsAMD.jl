@@ -407,6 +407,23 @@ function gap_safe(F::PackedF{R}, g::CiaoProxDesc, x::ROCArray{R,1}, γ::Real; co
     return (keep = keep, n_kept = n_kept, d = Int(F.d), s = s, kappa = κ, certificate = cert)
 end
 
+# Step sizes from the data (include/ciao_hip.h: ciao_row_sqnorms; Python twins: device.Context.row_sqnorms / row_sqnorm_stats,
+# stepsize.py; DESIGN.md section 8.9).  row_sqnorms: ‖a_i‖² per local row, Float64 whatever R is -- one pass over
+# A.  row_sqnorm_stats: (max, argmax (1-based), min, sum) of them from the same pass, without the N-vector.  The L = of the solvers is
+# λ‖a_i‖² (LeastSquares rows, test_lasso.jl:52-56) or ‖a_i‖²/4 (logistic rows, test_logistic_l1.jl:39).
+function row_sqnorms(F::PackedF{R}; out::ROCArray{Float64,1} = ROCArray{Float64}(undef, Int(F.N))) where {R}
+    check(ccall((:ciao_row_sqnorms, libciao), Int32, (Ptr{Cvoid}, Ref{CiaoProblem}, Ptr{Cvoid}, Ptr{Float64}),
+                context().h, Ref(cproblem(F)), dptr(out), Ptr{Float64}(C_NULL)))
+    return out
+end
+
+function row_sqnorm_stats(F::PackedF{R}) where {R}
+    stats = zeros(Float64, 4)
+    check(ccall((:ciao_row_sqnorms, libciao), Int32, (Ptr{Cvoid}, Ref{CiaoProblem}, Ptr{Cvoid}, Ptr{Float64}),
+                context().h, Ref(cproblem(F)), Ptr{Cvoid}(C_NULL), stats))
+    return (max = stats[1], argmax = Int(stats[2]) + 1, min = stats[3], sum = stats[4])
+end
+
 # ======================================================================================================================
 # SVRG  (src/algorithms/SVRG/SVRG.jl, SVRG_basic.jl)
 # ======================================================================================================================

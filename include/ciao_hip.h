@@ -242,6 +242,20 @@ CIAO_API int32_t ciao_col_sqnorms(ciao_ctx *ctx, const ciao_problem *p, double *
  * everything; NaN refused); mu > 0 and finite; d >= 1; no NULL argument: otherwise CIAO_ERR_ARG.  Synchronises. */
 CIAO_API int32_t ciao_screen(ciao_ctx *ctx, int32_t dtype, int64_t d, const void *grad, const double *colsq, double s, double kappa,
                              double mu, uint8_t *keep, int64_t *n_kept_host);
+/* EXTENSION beyond the reference: the per-sample smoothness constants of a packed matrix.  The reference's tests form them on the host
+ * from the rows, L_i = lam ||a_i||^2 (test/test_lasso.jl:52-56) and L_i = ||a_i||^2 / 4 (test/test_logistic_l1.jl:39), and every step
+ * size follows from them (gamma = 1 / (7 max L), test_lasso.jl:164; gamma_i = alpha N / L_i, Finito_basic.jl:61-74).  DESIGN.md section 8.9.
+ * Row sums of squares: out[i] = sum_j A[i,j]^2 for the N resident rows; out is a device vector of N DOUBLES whatever p->dtype is, or
+ * NULL.  stats_host: 4 host doubles {max_i out[i], the smallest i that attains it (exact as a double), min_i out[i], sum_i out[i]},
+ * or NULL; with out = NULL only the summary is produced and no N-vector exists anywhere.  One pass over A (every element read once,
+ * squares formed and added in double), no atomics: bitwise reproducible between runs, contexts, row strides and pointer alignments
+ * -- the order of addition of a row is a function of d alone, that of the summary of (N, d) alone.  A NaN anywhere in a row makes
+ * that row's value NaN and the summary's max, min and sum NaN (argmax: the first such row), so that a step size derived from it is
+ * NaN too.  CIAO_LOSS_LS, CIAO_LOSS_LOGISTIC and CIAO_LOSS_LS_COMPLEX problems (a complex row is its 2n reals: ||a_i||^2 is their
+ * sum of squares).  CIAO_LOSS_ZERO (no A), N = 0, a NULL problem and out = stats_host = NULL are refused with CIAO_ERR_ARG and
+ * nothing is launched.  On a row-sharded context: the LOCAL rows only, as ciao_row_dots and ciao_col_sqnorms.  Workspace: 128 KiB
+ * of records.  Synchronises only where stats_host is non-NULL (and where that workspace is first allocated). */
+CIAO_API int32_t ciao_row_sqnorms(ciao_ctx *ctx, const ciao_problem *p, double *out, double *stats_host);
 
 /* ---- SVRG / SVRG++  (SVRG/SVRG_basic.jl) -------------------------------------------------------------------- */
 /* Base.iterate(iter), :57-66: av = full gradient at x0; z_full = x0; z = 0; w = x0. */
