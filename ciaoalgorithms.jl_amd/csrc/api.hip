@@ -1715,6 +1715,42 @@ int32_t ciao_row_sqnorms(ciao_ctx *ctx, const ciao_problem *p, double *out, doub
     return DISPATCH(p->dtype, row_sqnorms_t, ctx, p, out, stats_host);
 }
 
+int32_t ciao_col_moments(ciao_ctx *ctx, const ciao_problem *p, const double *shift, double *s1, double *s2)
+{
+    CIAO_REQUIRE(ctx && p && s1 && s2, "ciao_col_moments: the context, the problem or one of the two output vectors is NULL");
+    CIAO_ENTER(ctx);
+    CIAO_TRY(check_problem(ctx, p));
+    CIAO_REQUIRE(p->loss != CIAO_LOSS_LS_COMPLEX, "ciao_col_moments covers real problems only (complex T: a column of (re, im) pairs has no real mean)");
+    CIAO_REQUIRE(p->loss != CIAO_LOSS_ZERO, "ciao_col_moments needs data rows (Zero() terms have no matrix A)");
+    if (p->N == 0) {   // a rank that holds no row: both sums are zero, nothing is launched
+        CIAO_HIP(hipMemsetAsync(s1, 0, (size_t)p->d * sizeof(double), ctx->stream));
+        CIAO_HIP(hipMemsetAsync(s2, 0, (size_t)p->d * sizeof(double), ctx->stream));
+        return CIAO_OK;
+    }
+    return p->dtype == CIAO_F64 ? launch_colmom<double>(ctx, p, shift, s1, s2) : launch_colmom<float>(ctx, p, shift, s1, s2);
+}
+
+int32_t ciao_scale_columns(ciao_ctx *ctx, const ciao_problem *p, const double *center, const double *scale, void *out, int64_t ld_out)
+{
+    CIAO_REQUIRE(ctx && p && (out || p->N == 0), "ciao_scale_columns: the context, the problem or the output matrix is NULL");
+    CIAO_ENTER(ctx);
+    CIAO_TRY(check_problem(ctx, p));
+    CIAO_REQUIRE(p->loss != CIAO_LOSS_LS_COMPLEX, "ciao_scale_columns covers real problems only (complex T: columns of (re, im) pairs are not scaled)");
+    CIAO_REQUIRE(p->loss != CIAO_LOSS_ZERO, "ciao_scale_columns needs data rows (Zero() terms have no matrix A)");
+    CIAO_REQUIRE(ld_out >= p->d, "ciao_scale_columns: the row stride of out, ld_out=%lld, is below d=%lld", (long long)ld_out, (long long)p->d);
+    if (p->N == 0) return CIAO_OK;
+    if (!(out == p->A && ld_out == p->ld)) {
+        // the bytes either matrix spans; out may be A itself (same stride: every element is read and written by one thread), nothing else
+        const size_t es = p->dtype == CIAO_F64 ? 8 : 4;
+        const uintptr_t a0 = reinterpret_cast<uintptr_t>(p->A), a1 = a0 + ((size_t)(p->N - 1) * (size_t)p->ld + (size_t)p->d) * es;
+        const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + ((size_t)(p->N - 1) * (size_t)ld_out + (size_t)p->d) * es;
+        CIAO_REQUIRE(o1 <= a0 || a1 <= o0, "ciao_scale_columns: out overlaps A without being A itself with the same row stride "
+                                           "(in place means out == A and ld_out == ld)");
+    }
+    return p->dtype == CIAO_F64 ? launch_colscale<double>(ctx, p, center, scale, out, ld_out)
+                                : launch_colscale<float>(ctx, p, center, scale, out, ld_out);
+}
+
 int32_t ciao_screen(ciao_ctx *ctx, int32_t dtype, int64_t d, const void *grad, const double *colsq, double s, double kappa, double mu,
                     uint8_t *keep, int64_t *n_kept_host)
 {

@@ -157,6 +157,15 @@ constexpr int ROWSQ_WS_DOUBLES = 8 + 2048 * 8;
 template <typename T>
 int32_t launch_rowsq(ciao_ctx *ctx, const ciao_problem *p, double *out, double *rec, double *res);
 
+// Column standardisation (colmom_kernels.h).  launch_colmom: s1[j] = sum_i (A[i,j] - c_j), s2[j] = sum_i (A[i,j] - c_j)^2 over the N local
+// rows, d device doubles each, c = shift (d device doubles) or the first local row (NULL); the partial d-vectors go to ctx->partial (grown
+// here).  launch_colscale: out[i,j] = (T)(((double)A[i,j] - center_j) * scale_j), NULL center = 0, NULL scale = 1; out may be p->A with
+// ld_out = p->ld.  Specialised in colmom_f32.hip / colmom_f64.hip.
+template <typename T>
+int32_t launch_colmom(ciao_ctx *ctx, const ciao_problem *p, const double *shift, double *s1, double *s2);
+template <typename T>
+int32_t launch_colscale(ciao_ctx *ctx, const ciao_problem *p, const double *center, const double *scale, void *out, int64_t ld_out);
+
 // ProShI agent rows (init or one batch) + finalize + epilogue.  Specialised in rows_f32.hip / rows_f64.hip.
 template <typename T>
 int32_t launch_proshi(ciao_ctx *ctx, bool init, ProshiArgs<T> &a, const Epilogue<T> &ep);

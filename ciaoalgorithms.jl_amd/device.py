@@ -526,6 +526,58 @@ class Context:
         self._row_sqnorms(F, None, stats)
         return RowNormStats(stats[0], int(stats[1]), stats[2], stats[3])
 
+    # -- column standardisation (standardize.py) -------------------------------------------------------
+    def _dvec(self, t, name, d):
+        """a float64 device d-vector, or None -> its pointer (None: NULL)"""
+        if t is None:
+            return None
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == d):
+            raise ValueError(f"{name}: need a contiguous float64 device vector of length {d}")
+        return _ptr(t)
+
+    def col_moments(self, F, shift=None, s1=None, s2=None):
+        """(s1, s2) with s1[j] = sum_i (A[i,j] - c_j) and s2[j] = sum_i (A[i,j] - c_j)^2 over the N local rows of F (include/ciao_hip.h:
+        ciao_col_moments) -> two device float64 d-vectors whatever F's dtype is.  c = shift, a float64 device d-vector, or (None) the
+        first local row.  One pass over A; bitwise reproducible.  Does not synchronise, except where the workspace of partial sums has
+        to grow."""
+        if isinstance(F, PackedSepQuad):
+            raise L.CiaoError(L.ERR_ARG, "column moments exist for LeastSquares / logistic rows, not for the sharing problem")
+        for v in (s1, s2):
+            if v is None:
+                continue
+            self._dvec(v, "s1 / s2", F.d)
+        if s1 is None or s2 is None:
+            both = torch.empty((2, F.d), dtype=torch.float64, device=f"cuda:{self.device}")
+            if self.stream is not None:
+                both.record_stream(self.stream)
+            s1 = both[0] if s1 is None else s1
+            s2 = both[1] if s2 is None else s2
+        L.check(self.lib.ciao_col_moments(self._h, F.ref, self._dvec(shift, "shift", F.d), _ptr(s1), _ptr(s2)))
+        return s1, s2
+
+    def scale_columns(self, F, center=None, scale=None, out=None, inplace=False):
+        """out[i,j] = T((float64(A[i,j]) - center_j) * scale_j) for the N local rows of F (include/ciao_hip.h: ciao_scale_columns) -> out.
+        center / scale: float64 device d-vectors; None means 0 / 1.  out: a row-major (N, d) device matrix of F's dtype (any row stride; its
+        padding columns are not written), a fresh one by default; inplace=True writes over F.A.  One pass: N d read, N d written.  Does not
+        synchronise."""
+        if isinstance(F, PackedSepQuad):
+            raise L.CiaoError(L.ERR_ARG, "columns are scaled for LeastSquares / logistic rows, not for the sharing problem")
+        if inplace:
+            if out is not None and out is not F.A:
+                raise ValueError("inplace=True writes over F.A: out must be None")
+            out = F.A
+        elif out is None and F.A is not None:
+            out = torch.empty((F.N, F.d), dtype=F.dtype, device=f"cuda:{self.device}")
+            if self.stream is not None:
+                out.record_stream(self.stream)
+        if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == F.dtype and out.dim() == 2
+                                    and tuple(out.shape) == (F.N, F.d) and (out.stride(1) == 1 or F.d == 1)):
+            raise ValueError(f"out: need a row-major device matrix of shape ({F.N}, {F.d}) and dtype {F.dtype}")
+        ld_out = F.d if out is None else (int(out.stride(0)) if F.N > 1 else F.d)
+        L.check(self.lib.ciao_scale_columns(self._h, F.ref, self._dvec(center, "center", F.d), self._dvec(scale, "scale", F.d),
+                                            _ptr(out) if out is not None else None, ld_out))
+        return out
+
     # -- SVRG ------------------------------------------------------------------------------------------------------------
     def svrg_init(self, p, x0, av, z, z_full, w):
         L.check(self.lib.ciao_svrg_init(self._h, p.ref, self._vec(x0, p, "x0"), self._vec(av, p, "av"), self._vec(z, p, "z"),

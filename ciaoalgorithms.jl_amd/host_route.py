@@ -445,6 +445,46 @@ def host_lipschitz(kind, A, lam=1.0):
     return (float(lam) if kind == "ls" else 0.25) * host_row_sqnorms(A)
 
 
+def host_col_moments(A, shift=None):
+    """The shifted column sums of ciao_col_moments in numpy (float64) -> (s1, s2): s1[j] = sum_i (A[i,j] - c_j), s2[j] = sum_i
+    (A[i,j] - c_j)^2 with c = shift or (None) the first row.  The differences and squares are what the device forms; the order of addition
+    is numpy's, so the two agree to (N + 2) 2^-53 sum|a - c| and (N + 3) 2^-53 sum (a - c)^2, and bitwise where every sum is exact."""
+    A = np.asarray(A)
+    if A.ndim != 2 or np.iscomplexobj(A):
+        raise ValueError("A must be a real N x d matrix")
+    A = A.astype(np.float64)
+    c = A[0] if shift is None else np.asarray(shift, dtype=np.float64)
+    t = A - c[None, :]
+    return np.sum(t, axis=0), np.sum(t * t, axis=0)
+
+
+def host_standardize(A, b=None, center=True, scale=True, refine=True):
+    """standardize.standardize in numpy on a host matrix -> (A_std, b_std, mean, scale, b_mean).  The moments are
+    standardize.host_column_moments' (the same shift, the same refinement rule, the same default: always refined); scale_j = 1 / sqrt(var_j) with the population variance, 1
+    where var_j = 0; A_std = ((float64(A) - mean) * scale) rounded to A's dtype once, which is bitwise what ciao_scale_columns computes
+    from the same mean and scale.  b (LeastSquares targets) is centred when `center`; pass None for logistic labels: b_std = None,
+    b_mean = 0.  center=False / scale=False leave mean = 0 / scale = 1."""
+    from .standardize import host_column_moments
+    A = np.asarray(A)
+    m = host_column_moments(A, refine=refine)
+    d = A.shape[1]
+    mean = m.mean if center else np.zeros(d)
+    sc = np.ones(d)
+    if scale:
+        nz = m.var > 0
+        sc[nz] = 1.0 / np.sqrt(m.var[nz])
+    A_std = ((A.astype(np.float64) - mean[None, :]) * sc[None, :]).astype(A.dtype)
+    b_mean, b_std = 0.0, None
+    if b is not None:
+        b = np.asarray(b)
+        if center:
+            b_mean = float(np.mean(b.astype(np.float64)))
+            b_std = (b.astype(np.float64) - b_mean).astype(b.dtype)
+        else:
+            b_std = b.copy()
+    return A_std, b_std, mean, sc, b_mean
+
+
 def announce(why):
     warnings.warn("CIAOAlgorithms (AMD): this problem runs on the HOST route -- numpy, one operator call per sample, no GPU -- "
                   f"because {why}.  It is orders of magnitude slower than the device path and none of this package's "

@@ -424,6 +424,62 @@ function row_sqnorm_stats(F::PackedF{R}) where {R}
     return (max = stats[1], argmax = Int(stats[2]) + 1, min = stats[3], sum = stats[4])
 end
 
+# Column standardisation (include/ciao_hip.h: ciao_col_moments, ciao_scale_columns; Python twins: device.Context.col_moments /
+# scale_columns, standardize.py; DESIGN.md section 8.10).  col_moments: s1[j] = Σ_i (A[i,j] - c_j), s2[j] = Σ_i (A[i,j] - c_j)², Float64
+# whatever R is, c = shift or (nothing) the first row -- one pass over A.  scale_columns!: out[i,j] = R((Float64(A[i,j]) - center_j) scale_j),
+# `nothing` for 0 / 1; out = F.A (the default) is in place.
+function col_moments(F::PackedF{R}; shift::Maybe{ROCArray{Float64,1}} = nothing) where {R}
+    s1 = ROCArray{Float64}(undef, Int(F.d)); s2 = ROCArray{Float64}(undef, Int(F.d))
+    check(ccall((:ciao_col_moments, libciao), Int32, (Ptr{Cvoid}, Ref{CiaoProblem}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                context().h, Ref(cproblem(F)), dptr(shift), dptr(s1), dptr(s2)))
+    return s1, s2
+end
+
+function scale_columns!(F::PackedF{R}; center::Maybe{ROCArray{Float64,1}} = nothing, scale::Maybe{ROCArray{Float64,1}} = nothing,
+                        out::ROCArray{R,2} = F.A) where {R}
+    size(out) == (Int(F.d), Int(F.N)) || throw(ArgumentError("out must be d x N column-major (N x d row-major, ld = d)"))
+    check(ccall((:ciao_scale_columns, libciao), Int32, (Ptr{Cvoid}, Ref{CiaoProblem}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64),
+                context().h, Ref(cproblem(F)), dptr(center), dptr(scale), dptr(out), Int64(F.d)))
+    return out
+end
+
+# mean = c + s1/N and population variance max(s2 - s1²/N, 0)/N of every column; a second pass about the mean where the first lost more
+# than ten bits to cancellation in some column (s2/M2 > 2^10, or M2 <= 0 < s2).  refine: :auto, true or false.
+function column_moments(F::PackedF{R}; refine = :auto) where {R}
+    (F.loss == LOSS_LS || F.loss == LOSS_LOGISTIC) || throw(ArgumentError("column moments need real LeastSquares or logistic rows"))
+    N = F.N
+    c = Float64.(F.A[:, 1])
+    s1, s2 = col_moments(F)
+    mean = c .+ s1 ./ N
+    passes = 1
+    M2 = s2 .- s1 .* s1 ./ N
+    if refine === true || (refine === :auto && any(((M2 .> 0) .& (s2 .> 2.0^10 .* M2)) .| ((M2 .<= 0) .& (s2 .> 0))))
+        s1, s2 = col_moments(F; shift = mean)
+        mean = mean .+ s1 ./ N
+        M2 = s2 .- s1 .* s1 ./ N
+        passes = 2
+    end
+    return (mean = mean, var = max.(M2, 0.0) ./ N, n = N, passes = passes)
+end
+
+# Centre every column at its mean and scale it to unit population variance (scale_j = 1 where var_j = 0: a constant column centred is
+# exactly zero); LeastSquares targets are centred too.  -> (F_std, (mean, scale, b_mean)); the model on the original columns is
+# x_j = x_std_j scale_j with the intercept b_mean - mean'x.  inplace = true writes over F.A.
+function standardize(F::PackedF{R}; center::Bool = true, scale::Bool = true, inplace::Bool = false, refine = true) where {R}
+    m = column_moments(F; refine = refine)
+    mean = center ? m.mean : nothing
+    sc = scale ? ifelse.(m.var .> 0, 1.0 ./ sqrt.(m.var), 1.0) : nothing
+    out = inplace ? F.A : similar(F.A)
+    scale_columns!(F; center = mean, scale = sc, out = out)
+    b, b_mean = F.b, 0.0
+    if center && F.loss == LOSS_LS
+        b_mean = sum(Float64.(F.b)) / F.N
+        b = R.(Float64.(F.b) .- b_mean)
+    end
+    Fs = PackedF{R}(F.loss, out, b, F.lam, F.N, F.d)
+    return Fs, (mean = center ? m.mean : zero(m.mean), scale = scale ? sc : one.(m.var), b_mean = b_mean)
+end
+
 # ======================================================================================================================
 # SVRG  (src/algorithms/SVRG/SVRG.jl, SVRG_basic.jl)
 # ======================================================================================================================

@@ -256,6 +256,33 @@ CIAO_API int32_t ciao_screen(ciao_ctx *ctx, int32_t dtype, int64_t d, const void
  * nothing is launched.  On a row-sharded context: the LOCAL rows only, as ciao_row_dots and ciao_col_sqnorms.  Workspace: 128 KiB
  * of records.  Synchronises only where stats_host is non-NULL (and where that workspace is first allocated). */
 CIAO_API int32_t ciao_row_sqnorms(ciao_ctx *ctx, const ciao_problem *p, double *out, double *stats_host);
+/* EXTENSION beyond the reference: the column moments of a packed matrix, for standardising it where it lies.  The reference has no
+ * counterpart (its tests build their matrices on the host); one l1 weight on columns of different scale penalises units, and
+ * LeastSquares rows have no intercept unless A and b are centred.  DESIGN.md section 8.10.
+ * Shifted sums over the N resident rows, for j < d:
+ *     s1[j] = sum_i (A[i,j] - c_j)        s2[j] = sum_i (A[i,j] - c_j)^2
+ * with c = shift, a device vector of d DOUBLES, or (shift = NULL) c_j = A[0,j], read by the kernel.  s1 and s2 are device vectors of d
+ * DOUBLES whatever p->dtype is.  (double)a - c_j, its square and every addition are formed in double, without contraction.  Then
+ * mean_j = c_j + s1[j] / N and M2_j = s2[j] - s1[j]^2 / N (N times the population variance), M2 with a relative error of at most
+ * 2 (N + 3) 2^-53 s2 / M2: where that quotient is large, a second call with shift = the mean brings it to 1.  One pass over A (every
+ * element read once), no atomics: bitwise reproducible between runs, contexts, row strides and pointer alignments -- every order of
+ * addition is a function of (N, d) alone.  Real CIAO_LOSS_LS / CIAO_LOSS_LOGISTIC problems; complex problems, CIAO_LOSS_ZERO (no A)
+ * and NULL ctx / p / s1 / s2 are refused with CIAO_ERR_ARG and nothing is launched.  N = 0: both vectors are set to zero, no kernel is
+ * launched.  On a row-sharded context: the LOCAL rows only, as ciao_col_sqnorms (with shift = NULL each rank would shift by its own
+ * first row: pass a common shift there).  Workspace: at most 32 MiB of partial sums (16 d bytes where that is more).  Does not
+ * synchronise, except where that workspace has to grow. */
+CIAO_API int32_t ciao_col_moments(ciao_ctx *ctx, const ciao_problem *p, const double *shift, double *s1, double *s2);
+/* EXTENSION beyond the reference: centre and scale the columns of a packed matrix in one pass.  For i < N, j < d:
+ *     out[i,j] = (T)( ((double)A[i,j] - center_j) * scale_j )
+ * center, scale: device vectors of d DOUBLES; NULL center means 0, NULL scale means 1.  One subtraction and one multiplication in
+ * double, without contraction, then one rounding to T.  out: device, N rows of stride ld_out >= d elements of p->dtype; the columns
+ * [d, ld_out) of a row are not written.  out == p->A with ld_out == p->ld is allowed (in place: every element is read and written by
+ * the same thread, a row is loaded before it is stored); any other overlap of the two matrices is refused.  N d elements read, N d
+ * written; 16-byte accesses where both bases and both strides are multiples of 16 bytes.  Refusals as ciao_col_moments (NULL ctx /
+ * p / out, complex problems, CIAO_LOSS_ZERO), plus ld_out < d: CIAO_ERR_ARG, nothing launched.  N = 0: nothing to do (out may then be NULL).  On a
+ * row-sharded context: the local rows.  No workspace; does not synchronise. */
+CIAO_API int32_t ciao_scale_columns(ciao_ctx *ctx, const ciao_problem *p, const double *center, const double *scale, void *out,
+                                    int64_t ld_out);
 
 /* ---- SVRG / SVRG++  (SVRG/SVRG_basic.jl) -------------------------------------------------------------------- */
 /* Base.iterate(iter), :57-66: av = full gradient at x0; z_full = x0; z = 0; w = x0. */
