@@ -78,16 +78,18 @@ def close(dev, ref, dtype, scale=8, what="", ref64=None, scale64=None, size=None
 
 
 def make(loss, A, b, lam_f, dtype, pad=0):
-    """(oracle Problem, device PackedF) over the same data; pad > 0 gives the device copy a row stride d+pad."""
+    """(oracle Problem, device PackedF) over the same data; pad > 0 gives the device copy a row stride d+pad, the padding columns
+    poisoned (tests/layouts.py): what a row's padding holds is unspecified input and must stay out of every result."""
     import torch
     from oracle import twin as O
     from ciaoalgorithms_jl_amd.device import PackedF
     import ciaoalgorithms_jl_amd._lib as L
+    import layouts
     op = O.Problem(loss, A, b, lam_f)
     N, d = A.shape
     tA = torch.from_numpy(A).cuda()
     if pad:
-        buf = torch.zeros((N, d + pad), dtype=tA.dtype, device="cuda")
+        buf = layouts.poisoned((N, d + pad), tA.dtype, "cuda")
         buf[:, :d] = tA
         tA = buf[:, :d]
     tb = torch.from_numpy(b).cuda()
