@@ -81,6 +81,51 @@ class Certificate:
         return (self.ctx if self.ctx is not None else it.ctx).certificate(F, g, x, self.gamma, samples=self.samples)
 
 
+def gaps_together(ctx, F, gs, xs, gamma):
+    """[Certificate(ctx, F, g_k, N, gamma, samples=True) at x_k for k < K] from TWO passes over A in all, whatever K is: the K
+    certificates of a regularisation path (one g per model: gs is a list of K device.ProxG, or one for all).
+
+    Pass 1, Context.full_gradient_multi: the K gradients.  Then, per model and without a pass, the reduction over the d coordinates
+    (ciao_certificate with av given) for the residual, ||grad f(x_k)||_inf and x_k . grad f(x_k).  Pass 2,
+    Context.margin_stats_multi at s_k = min(1, mu_k / ||grad f(x_k)||_inf): F(x_k) -- the log-loss sum / N, or lam sum r^2 / (2 N)
+    -- and the entropy of the logistic dual.  The gap is the lasso's (LeastSquares rows) or F + g + E / N (logistic rows) for
+    g_k = NormL1(mu_k), mu_k > 0, and nan elsewhere.  Each result agrees with its single-model certificate to rounding (other orders
+    of addition in both passes), not bitwise.  F: a device.PackedF; refused on a row-sharded context and for the sharing problem, as
+    Certificate(samples=True) is.  Synchronises."""
+    import torch
+    from . import _lib as L
+    from .device import PackedF
+    if not isinstance(F, PackedF):
+        raise L.CiaoError(L.ERR_ARG, "gaps_together covers finite sums of LeastSquares / logistic rows packed for the device (device.PackedF)")
+    if ctx.is_row_sharded():
+        raise L.CiaoError(L.ERR_ARG, "gaps_together on a row-sharded context: the per-sample sums would need an all-reduce of their own")
+    if not (gamma > 0 and math.isfinite(gamma)):
+        raise L.CiaoError(L.ERR_ARG, "gaps_together: gamma must be > 0 and finite")
+    xs = list(xs)
+    K = len(xs)
+    gs = list(gs) if isinstance(gs, (list, tuple)) else [gs] * K
+    if K < 1 or len(gs) != K:
+        raise L.CiaoError(L.ERR_ARG, f"gaps_together: {K} iterates and {len(gs)} regularisers (one g per model, at least one model)")
+    avs = [torch.empty_like(x) for x in xs]
+    ctx.full_gradient_multi(F, xs, avs)
+    parts, scal, mus = [], [], []
+    for g, x, av in zip(gs, xs, avs):
+        c = ctx.certificate(F, g, x, gamma, av=av)
+        mu = g.lam if (g is not None and g.kind == L.PROX_L1 and g.lam > 0) else None
+        parts.append(c)
+        mus.append(mu)
+        scal.append(1.0 if (mu is None or c.grad_inf == 0 or not c.grad_inf == c.grad_inf) else min(1.0, mu / c.grad_inf))
+    stats = ctx.margin_stats_multi(F, xs, scal)
+    out = []
+    for c, mu, st in zip(parts, mus, stats):
+        if F.loss == L.LOSS_LOGISTIC:
+            out.append(assemble(st.loss_sum / F.N_total, c.g, c.residual, c.grad_inf, c.x_dot_grad, c.box_violation, mu=mu,
+                                entropy=st.entropy, n=F.N_total))
+        else:
+            out.append(assemble(0.5 * F.lam * st.sum_r2 / F.N_total, c.g, c.residual, c.grad_inf, c.x_dot_grad, c.box_violation, mu=mu))
+    return out
+
+
 def stop_when(cert, gap=None, residual=None):
     """A callable for the functors' `stop=` keyword: true at the first checked state whose certificate meets EVERY bound given
     (gap <= gap, residual <= residual).  The last certificate is kept in `.last`."""

@@ -960,6 +960,20 @@ static int32_t margin_stats_t(ciao_ctx *ctx, const ciao_problem *p, const void *
     return CIAO_OK;
 }
 
+// K models' statistics: the one-pass kernel where it applies (mscore_launch.inc); otherwise, per model, exactly what ciao_row_dots
+// followed by ciao_margin_stats launch -- the dots go to ctx->rowdot (the SVRG chain's cache is invalid from here on).
+template <typename T>
+static int32_t margin_stats_multi_t(ciao_ctx *ctx, const ciao_problem *p, int K, const void *const *x, const double *s_host, double *out_host)
+{
+    if (mscore_supported<T>(ctx, p, K, x)) return launch_mscore<T>(ctx, p, K, x, s_host, out_host);
+    CIAO_TRY(ensure(ctx, &ctx->rowdot, &ctx->rowdot_bytes, (size_t)p->N * sizeof(T)));
+    for (int k = 0; k < K; ++k) {
+        CIAO_TRY(row_dots_t<T>(ctx, p, x[k], ctx->rowdot));
+        CIAO_TRY(margin_stats_t<T>(ctx, p, ctx->rowdot, s_host ? s_host[k] : 1.0, out_host + 4 * (size_t)k));
+    }
+    return CIAO_OK;
+}
+
 // The certificate with its per-sample terms: the certificate's pass with the row dots kept (ctx->rowdot: the SVRG chain's cache is
 // invalid from here on), the reduction over the d coordinates, then the reduction over the N samples with s formed on the device from
 // the first one's ||grad f||_inf -- no host round trip between the two --, one copy, one synchronisation.
@@ -1458,6 +1472,8 @@ int32_t ciao_ctx_set_option(ciao_ctx *ctx, const char *key, int64_t value)
         ctx->small_nb = value;
     } else if (!strcmp(key, "multi_rhs_off")) {
         ctx->mrhs_off = value != 0;
+    } else if (!strcmp(key, "mscore_off")) {
+        ctx->mscore_off = value != 0;
     } else if (!strcmp(key, "peer_timeout_s")) {
         CIAO_REQUIRE(value >= 1 && value <= 86400, "peer_timeout_s must be in 1..86400");
         ctx->peer_timeout_s = value;
@@ -1675,6 +1691,22 @@ int32_t ciao_margin_stats(ciao_ctx *ctx, const ciao_problem *p, const void *dots
     CIAO_REQUIRE(dots && out_host, "dots or out_host is NULL");
     CIAO_REQUIRE(s >= 0.0 && s <= 1.0, "the dual scaling s must lie in [0, 1] (got %g)", s);
     return DISPATCH(p->dtype, margin_stats_t, ctx, p, dots, s, out_host);
+}
+
+int32_t ciao_margin_stats_multi(ciao_ctx *ctx, const ciao_problem *p, int32_t K, const void *const *x, const double *s_host, double *out_host)
+{
+    CIAO_REQUIRE(ctx && p && x && out_host, "ciao_margin_stats_multi: the context, the problem, the pointer table or out_host is NULL");
+    CIAO_ENTER(ctx);
+    CIAO_TRY(check_problem(ctx, p));
+    CIAO_TRY(check_samples(p, "ciao_margin_stats_multi"));
+    CIAO_REQUIRE(p->N >= 1, "ciao_margin_stats_multi needs at least one sample (N = 0)");
+    CIAO_REQUIRE(K >= 1 && K <= 256, "ciao_margin_stats_multi: K must be in 1..256 (got %d)", K);
+    for (int k = 0; k < K; ++k) {
+        CIAO_REQUIRE(x[k], "ciao_margin_stats_multi: x[%d] is NULL", k);
+        CIAO_REQUIRE(!s_host || (s_host[k] >= 0.0 && s_host[k] <= 1.0), "ciao_margin_stats_multi: the dual scaling s[%d] must lie in [0, 1] (got %g)",
+                     k, s_host[k]);
+    }
+    return DISPATCH(p->dtype, margin_stats_multi_t, ctx, p, K, x, s_host, out_host);
 }
 
 int32_t ciao_certificate_samples(ciao_ctx *ctx, const ciao_problem *p, const ciao_prox_desc *g, const void *x, double gamma,

@@ -39,6 +39,7 @@ struct ciao_ctx {
     size_t mrhs_ptrs_bytes = 0;
     std::vector<void *> mrhs_host;   // their host staging copy
     int64_t mrhs_off = 0;       // option multi_rhs_off: K iterates as K single sweeps (testing)
+    int64_t mscore_off = 0;     // option mscore_off: K models' statistics as K times (row dots + reduction) (testing)
     size_t partial_bytes = 0;
     void *pextra = nullptr;    // per-block extra scalars
     size_t pextra_bytes = 0;

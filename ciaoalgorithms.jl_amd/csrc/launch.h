@@ -138,6 +138,14 @@ template <typename T>
 int32_t launch_mstat(ciao_ctx *ctx, int loss, int64_t N, const void *dots, const void *b, double s, const double *M_dev, double mu,
                      double *rec, double *out);
 
+// the same four doubles for K models in one pass over A (mscore_kernels.h: MFMA row dots, mstat_elem as their epilogue): 4 K host
+// doubles.  Records and results in ctx->partial, the pointer / scaling table in ctx->mrhs_ptrs (both grown there).  Specialised in
+// mscore_f32.hip / mscore_f64.hip.
+template <typename T>
+bool mscore_supported(const ciao_ctx *ctx, const ciao_problem *p, int K, const void *const *x);
+template <typename T>
+int32_t launch_mscore(ciao_ctx *ctx, const ciao_problem *p, int K, const void *const *x, const double *s_host, double *out_host);
+
 // Gap-safe screening (colsq_kernels.h).  launch_colsq: out[j] = sum_i A[i,j]^2 over the N local rows, d device doubles; the partial
 // d-vectors go to ctx->partial (grown here).  launch_screen: keep[k] = !(s |grad_k| + kappa sqrt(colsq_k) < mu) and their count into
 // *cnt (device); rec = workspace of CERT_GRID_CAP records.  Workspace of ciao_screen (ctx->cert): [0] the count, [8..) the records.

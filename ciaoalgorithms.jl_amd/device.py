@@ -466,6 +466,26 @@ class Context:
         L.check(self.lib.ciao_margin_stats(self._h, F.ref, self._vec(dots, F, "dots", F.N), float(s), out))
         return (LogisticStats if F.loss == L.LOSS_LOGISTIC else LeastSquaresStats)(*out)
 
+    def margin_stats_multi(self, F, xs, s=None):
+        """margin_stats of the row dots a_i'x_k for K iterates in ONE pass over A, without the N x K dots (include/ciao_hip.h:
+        ciao_margin_stats_multi) -> a list of K LogisticStats or LeastSquaresStats.  xs: a list of 1..256 device d-vectors; s: None
+        (= 1 for every model), one number, or K numbers in [0, 1].  Synchronises."""
+        if isinstance(F, PackedSepQuad):
+            raise L.CiaoError(L.ERR_ARG, "margin statistics exist for LeastSquares / logistic rows, not for the sharing problem")
+        xs = list(xs)
+        K = len(xs)
+        if s is None:
+            sv = None
+        else:
+            vals = [float(s)] * K if isinstance(s, (int, float)) else [float(v) for v in s]
+            if len(vals) != K:
+                raise L.CiaoError(L.ERR_ARG, f"margin_stats_multi: {len(vals)} scalings for {K} iterates")
+            sv = (C.c_double * max(K, 1))(*vals)
+        out = (C.c_double * (4 * max(K, 1)))()
+        L.check(self.lib.ciao_margin_stats_multi(self._h, F.ref, K, self._ptr_table(xs, F, "x"), sv, out))
+        kind = LogisticStats if F.loss == L.LOSS_LOGISTIC else LeastSquaresStats
+        return [kind(*out[4 * k:4 * k + 4]) for k in range(K)]
+
     # -- gap-safe screening (screening.py; DESIGN.md section 8.8) ----------------------------------------------------------
     def col_sqnorms(self, F, out=None):
         """out[j] = sum_i A[i,j]^2 over the N local rows of F (include/ciao_hip.h: ciao_col_sqnorms) -> a device float64 d-vector

@@ -362,6 +362,12 @@ def host_margin_stats(kind, dots, b, s=1.0):
     return (float(np.sum(np.maximum(-t, 0.0) + np.log1p(e))), float(np.sum(xlogx(v) + xlogx(w))), float(np.sum(t <= 0)), float(np.min(t)))
 
 
+def host_margin_stats_multi(kind, A, xs, b, s=None):
+    """ciao_margin_stats_multi in numpy (float64): K calls of host_margin_stats on the row dots A @ x_k, at s_k (None: 1)."""
+    A = np.asarray(A, np.float64)
+    return [host_margin_stats(kind, A @ np.asarray(x, np.float64).reshape(-1), b, 1.0 if s is None else float(s[k])) for k, x in enumerate(xs)]
+
+
 def _score(kind, stats, n):
     """scoring.score's fields from the four statistics."""
     from .scoring import LeastSquaresScore, LogisticScore

@@ -348,6 +348,35 @@ function margin_stats(F::PackedF{R}, dots::ROCArray{R,1}; s::Real = 1.0) where {
     return out
 end
 
+# margin_stats of the row dots a_i'x_k for K iterates (1 ≤ K ≤ 256) in ONE pass over the rows, without the N × K dots
+# (include/ciao_hip.h: ciao_margin_stats_multi; Python twin: device.Context.margin_stats_multi).  Returns a 4 × K matrix: column k holds
+# model k's four numbers.  s: one scaling per model in [0, 1], or nothing (= 1).
+function margin_stats_multi(F::PackedF{R}, xs::Vector{<:ROCArray{R}}; s::Maybe{Vector{Float64}} = nothing) where {R}
+    K = length(xs)
+    s === nothing || length(s) == K || throw(ArgumentError("as many scalings as iterates"))
+    xt = Ptr{Cvoid}[dptr(x) for x in xs]
+    out = zeros(Float64, 4, max(K, 1))
+    sp = s === nothing ? Ptr{Float64}(C_NULL) : pointer(s)
+    p = Ref(cproblem(F))
+    GC.@preserve xt s check(ccall((:ciao_margin_stats_multi, libciao), Int32, (Ptr{Cvoid}, Ref{CiaoProblem}, Int32, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}),
+                                  context().h, p, Int32(K), pointer(xt), sp, out))
+    return out[:, 1:K]
+end
+
+# The scores of K fitted models on the rows of F (the training rows, or new rows with the same d) from one pass (scoring.score_many):
+# LeastSquares rows (mse, r2, max_abs_residual), logistic rows (log_loss, accuracy, min_margin), as named tuples.
+function score_many(F::PackedF{R}, xs::Vector{<:ROCArray{R}}) where {R}
+    st, n = margin_stats_multi(F, xs), Float64(F.N)
+    return map(1:length(xs)) do k
+        if F.loss == LOSS_LOGISTIC
+            (log_loss = st[1, k] / n, accuracy = 1.0 - st[3, k] / n, min_margin = st[4, k])
+        else
+            tss = st[3, k] - st[2, k]^2 / n
+            (mse = st[1, k] / n, r2 = tss > 0 ? 1.0 - st[1, k] / tss : NaN, max_abs_residual = st[4, k])
+        end
+    end
+end
+
 # certificate(...) with the per-sample terms: the same eight fields, and for logistic rows with g = NormL1(μ), μ > 0 the duality gap
 # F + g + E(s)/N at the dual point u_i = s σ(−t_i), s = min(1, μ/‖∇f‖∞) formed on the device (DESIGN.md section 8.7).  `stats`: the
 # four numbers of margin_stats on the pass's own row dots.  Not on a row-sharded context.

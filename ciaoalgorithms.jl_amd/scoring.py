@@ -28,3 +28,26 @@ def score(ctx, F, x):
     from .host_route import _score
     stats = ctx.margin_stats(F, ctx.row_dots(F, x), 1.0)
     return _score("logistic" if F.loss == L.LOSS_LOGISTIC else "ls", tuple(stats), F.N)
+
+
+def score_many(ctx, F, xs):
+    """[score(ctx, F, x) for x in xs] from ONE pass over the rows of F (Context.margin_stats_multi: up to 256 models a call; the
+    N x K predictions never exist): the scores of a regularisation path, of folds or of restarts on held-out rows.  Each agrees with
+    its own score() to rounding (another order of addition).  Synchronises."""
+    from . import _lib as L
+    from .host_route import _score
+    kind = "logistic" if F.loss == L.LOSS_LOGISTIC else "ls"
+    return [_score(kind, tuple(st), F.N) for st in ctx.margin_stats_multi(F, xs)]
+
+
+def best(scores):
+    """The index of the score with the smallest log_loss (LogisticScore) or mse (LeastSquaresScore).  A NaN never wins; ties go to the
+    smaller index.  ValueError on an empty list or where every score is NaN."""
+    arg, val = -1, float("inf")
+    for k, sc in enumerate(scores):
+        v = sc.log_loss if hasattr(sc, "log_loss") else sc.mse
+        if v == v and (arg < 0 or v < val):
+            arg, val = k, v
+    if arg < 0:
+        raise ValueError("best: no score to choose from (an empty list, or every score is NaN)")
+    return arg

@@ -147,6 +147,7 @@ CIAO_API int32_t ciao_ctx_set_monitor(ciao_ctx *ctx, const ciao_prox_desc *g, do
  *                          (rows_wrow_kernel: index lists, and row blocks of up to 8192 rows) but rows_smallb_kernel / the tiles
  *   "wrow_rows_per_wave"   rows_wrow_kernel: rows a wave takes in a small batch before more workgroups are used (0 = 4)
  *   "multi_rhs_off"        1: ciao_full_gradient_multi / ciao_svrg_epoch_tail_multi run K single sweeps (testing)
+ *   "mscore_off"           1: ciao_margin_stats_multi runs K times (row dots + per-sample reduction) instead of its one-pass kernel (testing)
  *   "peer_timeout_s"       wall-clock bound of a peer-mailbox wait, seconds (default 30)
  *   "chain_no_dma"         the register-ring chain instead of the LDS-DMA one;  "chain_big": the any-length kernels at any d
  *   "chain_four_waves"     rows of up to 2 KiB (fp64: 4 KiB) on the four-wave chain instead of the single-wave one
@@ -217,6 +218,21 @@ CIAO_API int32_t ciao_row_dots(ciao_ctx *ctx, const ciao_problem *p, const void 
  * RMSE / R^2 of a fitted model (the reference's tests compute them outside) and the logistic duality gap.  0 <= s <= 1; N >= 1; real
  * T with data rows only.  Bitwise reproducible: the order of every sum is a function of N alone.  Synchronises. */
 CIAO_API int32_t ciao_margin_stats(ciao_ctx *ctx, const ciao_problem *p, const void *dots, double s, double *out_host);
+/* EXTENSION beyond the reference (as ciao_full_gradient_multi is): the same statistics for K models in ONE pass over A -- model
+ * selection over a regularisation path, folds or restarts.
+ * x: HOST array of K device pointers (d-vectors of p->dtype, 16-byte aligned, as ciao_full_gradient_multi takes them).
+ * s_host: K host doubles in [0,1], or NULL (= all 1).  out_host: 4*K host doubles.
+ * out_host[4k .. 4k+4) holds exactly the four numbers ciao_margin_stats documents, for the row dots a_i'x_k over the N local rows at
+ * s = s_k.  The N x K dots never exist in memory (csrc/mscore_kernels.h: the row dots on the matrix cores, the per-sample terms as
+ * their epilogue).  Model k's four numbers are bitwise the same whatever K is, whichever place k has in the list and whatever the
+ * other iterates hold (NaN included); the order of every sum is a function of (N, d, dtype) alone.  They agree with
+ * ciao_row_dots + ciao_margin_stats to rounding (another order of addition), not bitwise.  1 <= K <= 256.  The one-pass kernel takes
+ * every d <= 1024, every ld and every base of A; longer rows, iterates that are not 16-byte aligned and the option "mscore_off" run
+ * as K times (the ciao_row_dots pass + the reduction of ciao_margin_stats) inside the call, bitwise what those two calls give.
+ * Refused with CIAO_ERR_ARG and nothing launched: a NULL ctx, p, x or out_host, K outside 1..256, a NULL x[k], an s_k outside [0,1]
+ * or NaN, N = 0, CIAO_LOSS_ZERO and complex problems.  On a row-sharded context: the LOCAL rows, as ciao_row_dots.  Synchronises. */
+CIAO_API int32_t ciao_margin_stats_multi(ciao_ctx *ctx, const ciao_problem *p, int32_t K, const void *const *x,
+                                         const double *s_host, double *out_host);
 /* ciao_certificate with its per-sample terms.  out_host[0..5] are exactly ciao_certificate's six numbers (av = NULL: the call makes
  * its pass), [6..9] the four numbers of ciao_margin_stats on that pass's row dots with s = min(1, mu / ||grad f(x)||_inf) formed on
  * the device (mu = g->lam for CIAO_PROX_L1 with lam > 0; s = 1 otherwise, and where grad f(x) = 0).  For logistic rows and NormL1
