@@ -1,0 +1,325 @@
+// gram_kernels.h -- the second-order statistics of a packed matrix in ONE pass over its rows (ciao_gram):
+//      G = A'A (d x d)      u = A'b      colsum = A'1      bsum = {sum b, sum b^2}
+// all in double whatever the rows' type is.  The first pass of this family that is compute-bound: N d^2 flops (upper triangle) on N d
+// elements, so it runs on the matrix cores (v_mfma_f64_16x16x4_f64) and the rows reach them through LDS.
+//
+// Structure.  The d columns are cut into nb = ceil(d / 128) column blocks; only the nb (nb + 1) / 2 tiles (ib, jb) with jb >= ib exist.
+// grid = tiles x P row partitions (gram_plan, a pure function of (N, d)).  A workgroup = 4 waves owns one 128 x 128 tile of G over one
+// contiguous range of rows and walks it in chunks of 16 rows:
+//     1. the chunk's two panels (16 rows x 128 columns of block ib and of block jb; one panel where ib == jb) come from global memory a
+//        chunk ahead, coalesced (consecutive threads read consecutive 16-byte pieces of a row), are converted to double where the rows are
+//        fp32, and are parked row-major in LDS (two buffers in turn, one barrier per chunk);
+//     2. wave (wi, wj) of a 2 x 2 arrangement owns the 64 x 64 quarter: 4 x 4 MFMA tiles, 16 accumulators = 64 doubles per lane.  With the
+//        SAMPLE index as the MFMA's k, both operands have the same shape -- lane (l & 15 -> column, l >> 4 -> row of a 4-row group) -- so
+//        sixteen consecutive columns of four consecutive rows are read from the row-major LDS copy straight into operand layout: no
+//        transpose anywhere.  Per group of 4 rows: 8 LDS reads of one double per lane, 16 MFMAs.
+//     3. on a diagonal tile the quarter (1, 0) is the mirror of (0, 1) and is not needed.  Its wave computes the AUGMENTED columns instead:
+//        the B operand [b_n, 1, 0, ... 0] against the 8 sixteen-column pieces of the panel gives u (accumulator column 0) and colsum (column 1)
+//        for the tile's 128 columns, and against itself sum b^2, sum b (and the row count): the Gram matrix of the row [a_n, b_n, 1] without a
+//        column block of its own.  9 MFMAs per 4 rows against the other waves' 16.
+//   At the end every workgroup writes one record (the 128 x 128 partial tile; on diagonal tiles also u, colsum, bsum) into the workspace.
+//   gram_final_kernel adds a tile's P records in partition order, one thread per element, and writes G[i][j] and its mirror G[j][i] FROM
+//   THE SAME SUM for i <= j (elements below the diagonal of a diagonal tile are never read): both triangles hold the same bits.
+//   No atomics, no flags, no scratch: the hand-off is the kernel boundary.
+//
+// What is never read: columns [d, ld) of a row, rows outside the partition.  Chunks of 16 bytes that lie wholly in [0, d) of an existing
+// row are vector loads where the base of A and ld allow; everything else is read element by element under its own predicate and what does
+// not exist is 0 IN BOTH OPERANDS (the ones of the augmented column included), so padding that holds NaN never meets a multiply.
+//
+// Order of addition.  An element of a record: the rows of the partition in groups of four, each group by one MFMA onto the running sum;
+// then the P records in partition order.  A function of (N, d) alone: not of ld, of the base, of the rows' type (fp32 values are exact in
+// double and so is every product of two of them), of the NULL outputs, or of the run.
+#pragma once
+
+#include "ciao_common.h"
+
+namespace ciao {
+
+constexpr int GRAM_T = 128;                 // columns per block: the tile is GRAM_T x GRAM_T
+constexpr int GRAM_KC = 16;                 // rows per staged chunk
+constexpr int GRAM_BLOCK = 256;             // four waves, 2 x 2 quarters of 64 x 64
+constexpr int GRAM_PITCH = GRAM_T + 16;     // LDS row in doubles: consecutive rows start 128 bytes apart modulo the 256 bytes of banks
+constexpr int GRAM_OFF_U = GRAM_T * GRAM_T;          // a record: the tile, then u, colsum (128 each), then {sum b, sum b^2}
+constexpr int GRAM_OFF_CS = GRAM_OFF_U + GRAM_T;
+constexpr int GRAM_OFF_B = GRAM_OFF_CS + GRAM_T;
+constexpr int GRAM_REC = GRAM_OFF_B + 8;             // doubles per (tile, partition) record
+constexpr int GRAM_WG_TARGET = 2048;        // workgroups asked for (8 per CU, as colsq / rowsq / mscore)
+constexpr size_t GRAM_WS_BYTES = (size_t)256 << 20;
+constexpr int GRAM_MAX_D = 4096;
+constexpr int GRAM_FINAL_BLOCKS = GRAM_T * GRAM_T / GRAM_BLOCK;   // final-kernel workgroups per tile
+
+struct GramPlan {
+    int nb;          // column blocks
+    int ntiles;      // nb (nb + 1) / 2
+    int P;           // row partitions
+    int xcd;         // 1: the tiles of a partition share an XCD (P a multiple of 8)
+    int grid;        // ntiles * P
+    int64_t per;     // rows per partition: whole chunks
+    size_t ws_bytes;
+};
+
+// a pure function of (N, d); N >= 1, 1 <= d <= GRAM_MAX_D
+__host__ __device__ inline GramPlan gram_plan(int64_t N, int64_t d)
+{
+    GramPlan pl;
+    pl.nb = (int)((d + GRAM_T - 1) / GRAM_T);
+    pl.ntiles = pl.nb * (pl.nb + 1) / 2;
+    const int64_t cap = (int64_t)(GRAM_WS_BYTES / ((size_t)pl.ntiles * GRAM_REC * sizeof(double)));   // >= 3 at d = 4096
+    int64_t want = ((GRAM_WG_TARGET + pl.ntiles - 1) / pl.ntiles + 7) / 8 * 8;
+    if (want > cap) want = cap;
+    if (want >= 8) want = want / 8 * 8;
+    int64_t per = ((N + want - 1) / want + GRAM_KC - 1) / GRAM_KC * GRAM_KC;
+    if (per < GRAM_KC) per = GRAM_KC;
+    pl.per = per;
+    pl.P = (int)((N + per - 1) / per);
+    pl.xcd = pl.P % 8 == 0;
+#ifdef CIAO_GRAM_PLAIN_MAP   // experiment builds only (Makefile EXP=): the A/B of the two blockIdx maps on one shape (CHANGELOG)
+    pl.xcd = 0;
+#endif
+    pl.grid = pl.ntiles * pl.P;
+    pl.ws_bytes = (size_t)pl.grid * GRAM_REC * sizeof(double);
+    return pl;
+}
+
+// tile t -> (ib, jb), jb >= ib, row-major over the upper triangle of blocks
+__host__ __device__ inline void gram_tile(int t, int nb, int &ib, int &jb)
+{
+    int i = 0;
+    while (t >= nb - i) {
+        t -= nb - i;
+        ++i;
+    }
+    ib = i;
+    jb = i + t;
+}
+
+template <typename T>
+struct GramArgs {
+    const T *A;
+    const T *b;
+    int64_t ld, N, d;
+    int64_t per;     // rows per partition
+    int P, nb, ntiles, xcd;
+    int vec16;       // the base of A and ld are multiples of 16 bytes
+    double *rec;     // [tile][partition][GRAM_REC]
+};
+
+constexpr size_t gram_lds_bytes() { return (size_t)2 * 2 * GRAM_KC * GRAM_PITCH * sizeof(double); }
+
+template <typename T>
+__global__ void __launch_bounds__(GRAM_BLOCK) gram_partial_kernel(GramArgs<T> a)
+{
+    using M = MfmaOf<double>;
+    using Acc = typename M::acc;
+    constexpr int VEC = 16 / (int)sizeof(T);
+    typedef T Vld __attribute__((ext_vector_type(VEC)));
+    typedef double D2 __attribute__((ext_vector_type(2)));
+    constexpr int CPR = GRAM_T / VEC;                     // 16-byte chunks of a panel row
+    constexpr int NLD = GRAM_KC * CPR / GRAM_BLOCK;       // chunks per thread and panel
+    constexpr int PANEL = GRAM_KC * GRAM_PITCH;           // doubles of one parked panel
+    static_assert(NLD >= 1 && NLD * GRAM_BLOCK == GRAM_KC * CPR, "panel layout");
+    extern __shared__ __attribute__((aligned(16))) unsigned char gram_raw[];
+    double *lds = reinterpret_cast<double *>(gram_raw);   // [2 buffers][panel I, panel J][KC][PITCH]
+    const int tid = threadIdx.x;
+    const int lane = tid & (WAVE - 1);
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c = lane & 15, h = lane >> 4;
+    const int wi = w >> 1, wj = w & 1;
+
+    // blockIdx -> (row partition, tile): with P a multiple of 8 the tiles of one partition are consecutive slots of ONE XCD (workgroups
+    // go to XCDs round-robin by blockIdx), so the nb panels of a chunk come from HBM once and from that XCD's L2 for the other tiles
+    // (mrhs_kernels.h).  Which workgroup takes which pair changes no result.
+    int part, t;
+    if (a.xcd) {
+        part = (blockIdx.x & 7) + 8 * (int)((blockIdx.x >> 3) / a.ntiles);
+        t = (int)((blockIdx.x >> 3) % a.ntiles);
+    } else {
+        part = (int)(blockIdx.x / a.ntiles);
+        t = (int)(blockIdx.x % a.ntiles);
+    }
+    int ib, jb;
+    gram_tile(t, a.nb, ib, jb);
+    const bool diag = ib == jb;
+    const bool augwave = diag && w == 2;   // quarter (1, 0) of a diagonal tile: the augmented columns instead
+    const int64_t r_lo = (int64_t)part * a.per;
+    const int64_t r_hi = r_lo + a.per < a.N ? r_lo + a.per : a.N;
+    const int64_t ci0 = (int64_t)ib * GRAM_T, cj0 = (int64_t)jb * GRAM_T;
+
+    // one panel of the chunk at t0, staged in registers: chunk q = 256 i + tid is chunk q % CPR of row q / CPR
+    Vld stI[NLD], stJ[NLD];
+    auto load_panel = [&](Vld(&st)[NLD], int64_t c0, int64_t t0) {
+        const bool whole = a.vec16 && t0 + GRAM_KC <= r_hi && c0 + GRAM_T <= a.d;   // (uniform in the workgroup)
+        if (whole) {
+#pragma unroll
+            for (int i = 0; i < NLD; ++i) {
+                const int q = i * GRAM_BLOCK + tid;
+                st[i] = *reinterpret_cast<const Vld *>(a.A + (t0 + q / CPR) * a.ld + (c0 + (q % CPR) * VEC));
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < NLD; ++i) {
+                const int q = i * GRAM_BLOCK + tid;
+                const int64_t row = t0 + q / CPR;
+                const int64_t col = c0 + (q % CPR) * VEC;
+                const T *src = a.A + row * a.ld + col;
+                if (a.vec16 && row < r_hi && col + VEC <= a.d) {
+                    st[i] = *reinterpret_cast<const Vld *>(src);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < VEC; ++e) st[i][e] = (row < r_hi && col + e < a.d) ? src[e] : T(0);
+                }
+            }
+        }
+    };
+    auto park_panel = [&](const Vld(&st)[NLD], double *dst) {
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            const int q = i * GRAM_BLOCK + tid;
+            double *o = dst + (q / CPR) * GRAM_PITCH + (q % CPR) * VEC;
+#pragma unroll
+            for (int e = 0; e < VEC; e += 2) {
+                D2 v;
+                v[0] = (double)st[i][e];
+                v[1] = (double)st[i][e + 1];
+                *reinterpret_cast<D2 *>(o + e) = v;
+            }
+        }
+    };
+    // the augmented B operand of a chunk, lane (column c, slot h), step ks: row t0 + 4 ks + h of [b, 1, 0 ... 0]; 0 where the row does not exist
+    double augn[GRAM_KC / 4] = {}, aug[GRAM_KC / 4];
+    auto load_aug = [&](int64_t t0) {
+#pragma unroll
+        for (int ks = 0; ks < GRAM_KC / 4; ++ks) {
+            const int64_t row = t0 + 4 * ks + h;
+            double v = 0.0;
+            if (row < r_hi) {
+                if (c == 0) v = (double)a.b[row];
+                if (c == 1) v = 1.0;
+            }
+            augn[ks] = v;
+        }
+    };
+
+    Acc acc[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = Acc(0.0);
+
+    if (r_lo < r_hi) {
+        load_panel(stI, ci0, r_lo);
+        if (!diag) load_panel(stJ, cj0, r_lo);
+        if (augwave) load_aug(r_lo);
+        park_panel(stI, lds);
+        if (!diag) park_panel(stJ, lds + PANEL);
+    }
+    __syncthreads();
+    int buf = 0;
+    for (int64_t t0 = r_lo; t0 < r_hi; t0 += GRAM_KC) {   // (uniform in the workgroup)
+        const bool next = t0 + GRAM_KC < r_hi;
+#pragma unroll
+        for (int ks = 0; ks < GRAM_KC / 4; ++ks) aug[ks] = augn[ks];
+        if (next) {
+            load_panel(stI, ci0, t0 + GRAM_KC);
+            if (!diag) load_panel(stJ, cj0, t0 + GRAM_KC);
+            if (augwave) load_aug(t0 + GRAM_KC);
+        }
+        const double *sI = lds + (size_t)buf * 2 * PANEL;
+        const double *sJ = diag ? sI : sI + PANEL;
+        if (!augwave) {
+            const double *pI = sI + h * GRAM_PITCH + wi * 64 + c;
+            const double *pJ = sJ + h * GRAM_PITCH + wj * 64 + c;
+#pragma unroll
+            for (int ks = 0; ks < GRAM_KC / 4; ++ks) {
+                double av[4], bv[4];
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    av[s] = pI[ks * 4 * GRAM_PITCH + s * 16];
+                    bv[s] = pJ[ks * 4 * GRAM_PITCH + s * 16];
+                }
+#pragma unroll
+                for (int si = 0; si < 4; ++si)
+#pragma unroll
+                    for (int sj = 0; sj < 4; ++sj) acc[si * 4 + sj] = M::mma(av[si], bv[sj], acc[si * 4 + sj]);
+            }
+        } else {
+            const double *pI = sI + h * GRAM_PITCH + c;
+#pragma unroll
+            for (int ks = 0; ks < GRAM_KC / 4; ++ks) {
+                double av[8];
+#pragma unroll
+                for (int s = 0; s < 8; ++s) av[s] = pI[ks * 4 * GRAM_PITCH + s * 16];
+#pragma unroll
+                for (int s = 0; s < 8; ++s) acc[s] = M::mma(av[s], aug[ks], acc[s]);
+                acc[8] = M::mma(aug[ks], aug[ks], acc[8]);
+            }
+        }
+        if (next) {
+            double *dst = lds + (size_t)(buf ^ 1) * 2 * PANEL;
+            park_panel(stI, dst);
+            if (!diag) park_panel(stJ, dst + PANEL);
+        }
+        __syncthreads();
+        buf ^= 1;
+    }
+
+    // ---- the workgroup's record.  Accumulator lane (c, h), register q: row M::row(h, q), column c of its 16 x 16 piece.
+    double *rec = a.rec + ((size_t)t * a.P + part) * GRAM_REC;
+    if (!augwave) {
+#pragma unroll
+        for (int si = 0; si < 4; ++si)
+#pragma unroll
+            for (int sj = 0; sj < 4; ++sj)
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    rec[(wi * 64 + si * 16 + M::row(h, q)) * GRAM_T + wj * 64 + sj * 16 + c] = acc[si * 4 + sj][q];
+    } else {
+        if (c < 2) {
+            double *o = rec + (c == 0 ? GRAM_OFF_U : GRAM_OFF_CS);
+#pragma unroll
+            for (int s = 0; s < 8; ++s)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) o[s * 16 + M::row(h, q)] = acc[s][q];
+            // [b, 1]'[b, 1]: row 0 (h = 0, q = 0), column 0: sum b^2; column 1: sum b
+            if (h == 0) rec[GRAM_OFF_B + (c == 0 ? 1 : 0)] = acc[8][0];
+        }
+    }
+}
+
+// Workgroups [0, 64 ntiles): 256 elements of a tile each, thread = element (i, j): the P records in partition order, then G[i][j] and
+// its mirror from the same sum.  Workgroups [64 ntiles, 64 ntiles + nb): u (threads 0 .. 127) and colsum (128 .. 255) of a column block, from
+// the records of its diagonal tile.  The last workgroup: bsum, from the records of tile 0.  NULL outputs are skipped.  (T only keeps the two
+// units' copies apart.)
+template <typename T>
+__global__ void __launch_bounds__(GRAM_BLOCK) gram_final_kernel(int64_t d, int nb, int ntiles, int P, const double *rec, double *G, int64_t ldg,
+                                                                 double *u, double *colsum, double *bsum)
+{
+    const int blk = blockIdx.x, tid = threadIdx.x;
+    if (blk < ntiles * GRAM_FINAL_BLOCKS) {
+        const int t = blk / GRAM_FINAL_BLOCKS, e = (blk % GRAM_FINAL_BLOCKS) * GRAM_BLOCK + tid;
+        int ib, jb;
+        gram_tile(t, nb, ib, jb);
+        const int64_t gi = (int64_t)ib * GRAM_T + e / GRAM_T, gj = (int64_t)jb * GRAM_T + e % GRAM_T;
+        if (gi >= d || gj >= d || gi > gj) return;
+        const double *q = rec + (size_t)t * P * GRAM_REC + e;
+        double s = 0.0;
+        for (int p = 0; p < P; ++p) s += q[(size_t)p * GRAM_REC];
+        G[gi * ldg + gj] = s;
+        if (gi != gj) G[gj * ldg + gi] = s;
+    } else if (blk < ntiles * GRAM_FINAL_BLOCKS + nb) {
+        const int ib = blk - ntiles * GRAM_FINAL_BLOCKS;
+        double *out = tid < GRAM_T ? u : colsum;
+        const int64_t col = (int64_t)ib * GRAM_T + (tid & (GRAM_T - 1));
+        if (!out || col >= d) return;
+        const int t = ib * nb - ib * (ib - 1) / 2;   // the diagonal tile (ib, ib)
+        const double *q = rec + (size_t)t * P * GRAM_REC + GRAM_OFF_U + tid;
+        double s = 0.0;
+        for (int p = 0; p < P; ++p) s += q[(size_t)p * GRAM_REC];
+        out[col] = s;
+    } else if (bsum && tid < 2) {
+        const double *q = rec + GRAM_OFF_B + tid;
+        double s = 0.0;
+        for (int p = 0; p < P; ++p) s += q[(size_t)p * GRAM_REC];
+        bsum[tid] = s;
+    }
+}
+
+}  // namespace ciao

@@ -174,6 +174,12 @@ int32_t launch_colmom(ciao_ctx *ctx, const ciao_problem *p, const double *shift,
 template <typename T>
 int32_t launch_colscale(ciao_ctx *ctx, const ciao_problem *p, const double *center, const double *scale, void *out, int64_t ld_out);
 
+// Gram statistics (gram_kernels.h).  launch_gram: G = A'A (d x d device doubles at row stride ldg, both triangles), u = A'b, colsum = A'1
+// (d device doubles each, or NULL), bsum = {sum b, sum b^2} (2 device doubles, or NULL) over the N >= 1 local rows; the records of
+// gram_plan(N, d) go to ctx->partial (grown here).  Specialised in gram_f32.hip / gram_f64.hip.
+template <typename T>
+int32_t launch_gram(ciao_ctx *ctx, const ciao_problem *p, double *G, int64_t ldg, double *u, double *colsum, double *bsum);
+
 // ProShI agent rows (init or one batch) + finalize + epilogue.  Specialised in rows_f32.hip / rows_f64.hip.
 template <typename T>
 int32_t launch_proshi(ciao_ctx *ctx, bool init, ProshiArgs<T> &a, const Epilogue<T> &ep);

@@ -598,6 +598,44 @@ class Context:
                                             _ptr(out) if out is not None else None, ld_out))
         return out
 
+    # -- Gram statistics (gram.py) -------------------------------------------------------------------
+    def gram(self, F, G=None, u=True, colsum=True, bsum=True):
+        """(G, u, colsum, bsum) with G = A'A (d x d), u = A'b, colsum = A'1 and bsum = (sum b, sum b^2) over the N local rows of F
+        (include/ciao_hip.h: ciao_gram) -> device float64 tensors whatever F's dtype is; fp32 rows give the bits their .double() copy
+        gives.  G: a row-major float64 device matrix of d rows (any row stride >= d; columns beyond d are not written), a fresh one by
+        default; both triangles are written with the same bits.  u / colsum / bsum: a float64 device vector (d, d, 2 elements) to write
+        into, True for a fresh one, or None / False to leave it out (NULL: the others' bits do not change).  One pass over A on the
+        matrix cores, paid once per dataset; bitwise reproducible.  d <= 4096.  Does not synchronise, except where the workspace of
+        partial tiles has to grow."""
+        if isinstance(F, PackedSepQuad):
+            raise L.CiaoError(L.ERR_ARG, "the Gram matrix exists for LeastSquares / logistic rows, not for the sharing problem")
+        dev = f"cuda:{self.device}"
+        d = F.d
+
+        def fresh(*shape):
+            t = torch.empty(shape, dtype=torch.float64, device=dev)
+            if self.stream is not None:
+                t.record_stream(self.stream)
+            return t
+
+        if G is None:
+            G = fresh(d, d)
+        if not (isinstance(G, torch.Tensor) and G.is_cuda and G.dtype == torch.float64 and G.dim() == 2 and tuple(G.shape) == (d, d)
+                and (G.stride(1) == 1 or d == 1)):
+            raise ValueError(f"G: need a row-major float64 device matrix of shape ({d}, {d})")
+        ldg = int(G.stride(0)) if d > 1 else d
+        outs = []
+        for v, name, n in ((u, "u", d), (colsum, "colsum", d), (bsum, "bsum", 2)):
+            if v is None or v is False:
+                outs.append(None)
+            elif v is True:
+                outs.append(fresh(n))
+            else:
+                self._dvec(v, name, n)
+                outs.append(v)
+        L.check(self.lib.ciao_gram(self._h, F.ref, _ptr(G), ldg, *(None if v is None else _ptr(v) for v in outs)))
+        return (G, *outs)
+
     # -- SVRG ------------------------------------------------------------------------------------------------------------
     def svrg_init(self, p, x0, av, z, z_full, w):
         L.check(self.lib.ciao_svrg_init(self._h, p.ref, self._vec(x0, p, "x0"), self._vec(av, p, "av"), self._vec(z, p, "z"),

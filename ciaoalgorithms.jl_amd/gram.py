@@ -1,0 +1,278 @@
+"""Second-order statistics of a packed matrix, and what follows from them without reading the matrix again.
+
+One pass over the rows on the matrix cores (include/ciao_hip.h: ciao_gram; csrc/gram_kernels.h) leaves G = A'A, u = A'b, A'1, sum b and
+sum b^2 in double.  From these d x d numbers alone:
+
+    st = gram_stats(ctx, F)                                  # the one pass over A
+    L_f = smoothness_exact(st)                               # lam lambda_max(G) / N: the constant stepsize.smoothness brackets
+    q = GramLasso(st)                                        # LeastSquares rows: grad f(x) = lam (G x - u) / N, F(x), certified gaps
+    path = lasso_path(st, [mu_max(st) * 0.5 ** k for k in range(1, 9)])
+    solve_together(..., x0=path.x)                           # exact warm starts; score_many(ctx, F_val, path.x) takes them as they are
+    st_std, sc = st.standardized()                           # the statistics of the standardised columns, A untouched
+
+Everything past gram_stats works on torch tensors of ANY device (GramStats.to moves them): a d x d problem is often best solved on
+the host, and the CPU tests feed these functions host_route.host_gram's numbers.  Nothing here is called by solvers.py.
+"""
+from __future__ import annotations
+
+import math
+from typing import NamedTuple
+
+from . import _lib as L
+from .certificate import CertificateResult, assemble
+
+AMPLIFICATION_LIMIT = 2.0 ** 10   # standardize.REFINE_RATIO: beyond it, standardise the matrix itself
+EPS = 2.0 ** -53
+
+
+class GramStats(NamedTuple):
+    N: int            # rows summed
+    d: int
+    G: object         # (d, d) float64 tensor, A'A, symmetric to the bit
+    u: object         # (d,) float64, A'b (b: LeastSquares targets, logistic labels)
+    colsum: object    # (d,) float64, A'1
+    sum_b: float
+    sum_bb: float
+    lam: float        # LeastSquares(a, b, lam)'s lam; 1.0 for logistic rows
+    kind: str         # "ls" or "logistic"
+    dtype: object = None   # the dtype of the rows the statistics came from (lasso_path returns iterates in it); None: float64
+
+    def to(self, device):
+        """The same statistics with their tensors on another device."""
+        return self._replace(G=self.G.to(device), u=self.u.to(device), colsum=self.colsum.to(device))
+
+    def standardized(self, center=True, scale=True):
+        """The statistics the standardised matrix WOULD have -> (GramStats, standardize.Scaler), from G, A'1 and N alone:
+
+            mean_j = colsum_j / N        var_j = G_jj / N - mean_j^2        scale_j = 1 / sqrt(var_j), and 1 where var_j = 0
+            G_std = D (G - N mean mean') D        u_std = D (u - mean sum_b)        D = diag(scale)
+
+        (center=False: no mean is taken off; scale=False: D = I).  LeastSquares targets are centred with the columns, as
+        standardize.standardize centres them: sum_b becomes 0 and sum_bb loses sum_b^2 / N; logistic labels stay.  The Scaler maps
+        solutions back (Scaler.coefficients) and carries `amplification`, a float64 d-vector: G_jj / (N var_j) = 1 + mean_j^2 / var_j,
+        the factor by which the subtraction G_jj - N mean_j^2 magnifies G's own rounding.  A column whose mean is a
+        thousand standard deviations loses twenty bits here.  Where the amplification of some column exceeds 2^10
+        (AMPLIFICATION_LIMIT, the rule of section 8.10), standardise the matrix itself -- standardize.standardize, which subtracts the
+        mean from every entry before anything is squared -- and take gram_stats of the result."""
+        import torch
+        from .standardize import Scaler
+        n = float(self.N)
+        G, u = self.G, self.u
+        mean = self.colsum / n
+        diag = torch.diagonal(G)
+        var = torch.clamp(diag / n - mean * mean, min=0.0)
+        amp = torch.where(var > 0, diag / (n * var), torch.where(diag > 0, torch.full_like(var, math.inf), torch.ones_like(var)))
+        sc = torch.where(var > 0, 1.0 / torch.sqrt(var), torch.ones_like(var)) if scale else torch.ones_like(var)
+        sum_b, sum_bb, colsum = self.sum_b, self.sum_bb, self.colsum
+        b_mean = 0.0
+        if center:
+            G = G - n * torch.outer(mean, mean)   # (outer's products commute: still symmetric to the bit)
+            u = u - mean * sum_b
+            colsum = torch.zeros_like(colsum)
+            if self.kind == "ls":
+                b_mean = sum_b / n
+                sum_bb = max(sum_bb - sum_b * sum_b / n, 0.0)
+                sum_b = 0.0
+        else:
+            mean = torch.zeros_like(mean)
+        G = G * torch.outer(sc, sc)               # (one product per entry, with a symmetric factor: symmetric to the bit)
+        scaler = Scaler(mean, sc, b_mean, center, scale)
+        scaler.amplification = amp
+        return self._replace(G=G, u=sc * u, colsum=sc * colsum, sum_b=sum_b, sum_bb=sum_bb), scaler
+
+
+def gram_stats(ctx, F) -> GramStats:
+    """One pass over the rows of F (Context.gram) -> GramStats on F's device.  F: a device.PackedF of real LeastSquares or logistic rows
+    with d <= 4096; refused on a row-sharded context (the ranks' matrices would have to be added).  Synchronises (the two sums of b
+    cross to the host)."""
+    from .device import PackedF
+    from .stepsize import _on_stream
+    if not isinstance(F, PackedF) or F.loss not in (L.LOSS_LS, L.LOSS_LOGISTIC):
+        raise L.CiaoError(L.ERR_ARG, "gram_stats covers device.PackedF problems of real LeastSquares or logistic rows: complex rows, the "
+                                     "sharing family and Zero terms have no Gram statistics here")
+    if ctx.is_row_sharded() or F.N_total != F.N:
+        raise L.CiaoError(L.ERR_ARG, "gram_stats on a row-sharded context (all-reduce hook, shard table, peers or a row shard): the ranks' "
+                                     "Gram matrices are not combined")
+    if F.N < 1:
+        raise L.CiaoError(L.ERR_ARG, "gram_stats needs at least one row (N = 0)")
+    G, u, colsum, bsum = ctx.gram(F)
+    with _on_stream(ctx):
+        sb = bsum.cpu()
+    ls = F.loss == L.LOSS_LS
+    return GramStats(int(F.N), int(F.d), G, u, colsum, float(sb[0]), float(sb[1]), float(F.lam) if ls else 1.0, "ls" if ls else "logistic",
+                     F.dtype)
+
+
+def host_gram_stats(A, b, lam=1.0, kind="ls") -> GramStats:
+    """GramStats from host_route.host_gram on a host matrix (numpy), as CPU torch tensors."""
+    import numpy as np
+    import torch
+    from .host_route import host_gram
+    if kind not in ("ls", "logistic"):
+        raise ValueError(f"kind must be 'ls' or 'logistic' (got {kind!r})")
+    A = np.asarray(A)
+    G, u, colsum, bsum = host_gram(A, b)
+    dt = torch.float32 if A.dtype == np.float32 else torch.float64
+    return GramStats(A.shape[0], A.shape[1], torch.from_numpy(G), torch.from_numpy(u), torch.from_numpy(colsum), float(bsum[0]), float(bsum[1]),
+                     float(lam) if kind == "ls" else 1.0, kind, dt)
+
+
+def smoothness_exact(stats: GramStats) -> float:
+    """The smoothness constant of f = (1/N) sum_i f_i, exactly: lam lambda_max(G) / N for LeastSquares rows, lambda_max(G) / (4 N) for
+    logistic rows (sigma' <= 1/4), from one torch.linalg.eigvalsh of the d x d matrix.  stepsize.smoothness brackets this number
+    (estimate <= it <= upper) with up to fifty passes over A."""
+    import torch
+    c = stats.lam if stats.kind == "ls" else 0.25
+    return c * float(torch.linalg.eigvalsh(stats.G)[-1]) / stats.N
+
+
+def mu_max(stats: GramStats) -> float:
+    """lam ||u||_inf / N = ||grad f(0)||_inf: the smallest l1 weight at which x = 0 minimises the lasso (LeastSquares rows)."""
+    _need_ls(stats, "mu_max")
+    return stats.lam * float(stats.u.abs().max()) / stats.N
+
+
+def _need_ls(stats, what):
+    if stats.kind != "ls":
+        raise L.CiaoError(L.ERR_ARG, f"{what} needs the statistics of LeastSquares rows: the logistic loss is not a function of A'A and A'b "
+                                     "(a Gram route for logistic solves is not built)")
+
+
+def _soft(v, tau):
+    import torch
+    return torch.sign(v) * torch.clamp(v.abs() - tau, min=0.0)
+
+
+class GramLasso:
+    """f(x) = (1/N) sum_i (lam / 2)(a_i'x - b_i)^2 in d-space, from GramStats of LeastSquares rows (logistic stats are refused):
+
+        gradient(x) = lam (G x - u) / N                    value(x) = lam (x'G x - 2 u'x + sum_bb) / (2 N)
+
+    x: a float64-convertible d-vector, or a d x K matrix of K iterates (K values / K gradient columns), on G's device.  value is a
+    difference of large terms: value_floor(x) = 4 * 2^-53 lam (x'Gx + 2 |u'x| + sum_bb) / (2 N) is what their rounding can amount to, and
+    a gap below it means nothing."""
+
+    def __init__(self, stats: GramStats):
+        _need_ls(stats, "GramLasso")
+        self.stats = stats
+
+    def _x(self, x):
+        import torch
+        if not isinstance(x, torch.Tensor):
+            x = torch.as_tensor(x)
+        return x.to(device=self.stats.G.device, dtype=torch.float64)
+
+    def gradient(self, x):
+        s = self.stats
+        x = self._x(x)
+        return (s.lam / s.N) * (s.G @ x - (s.u if x.dim() == 1 else s.u[:, None]))
+
+    def _terms(self, x):
+        s = self.stats
+        x = self._x(x)
+        Gx = s.G @ x
+        return (x * Gx).sum(0), (s.u if x.dim() == 1 else s.u[:, None]).mul(x).sum(0)
+
+    def value(self, x):
+        s = self.stats
+        q, l = self._terms(x)
+        v = (s.lam / (2.0 * s.N)) * (q - 2.0 * l + s.sum_bb)
+        return float(v) if v.dim() == 0 else v
+
+    def value_floor(self, x):
+        s = self.stats
+        q, l = self._terms(x)
+        v = 4.0 * EPS * (s.lam / (2.0 * s.N)) * (q + 2.0 * l.abs() + s.sum_bb)
+        return float(v) if v.dim() == 0 else v
+
+    def certificate(self, x, mu, gamma) -> CertificateResult:
+        """Context.certificate(F, NormL1(mu), x, gamma) without a pass over A: the same eight numbers through certificate.assemble.  mu: the
+        l1 weight (mu = 0 or None: g = Zero, the gap is nan); gamma: the step of the prox residual."""
+        if not (gamma > 0 and math.isfinite(gamma)):
+            raise ValueError("gamma must be > 0 and finite")
+        x = self._x(x)
+        if x.dim() != 1:
+            raise ValueError("certificate takes one iterate (a d-vector)")
+        mu_ = float(mu) if mu else 0.0
+        grad = self.gradient(x)
+        res = x - _soft(x - gamma * grad, gamma * mu_)
+        return assemble(self.value(x), mu_ * float(x.abs().sum()), float(res.norm()) / gamma, float(grad.abs().max()), float(x @ grad), 0.0,
+                        mu=mu_ if mu_ > 0 else None)
+
+    def as_certificate(self, mu, gamma):
+        """A callable state -> CertificateResult for certificate.stop_when: the stop check of a solve over the same rows then costs a
+        d x d product instead of a pass over A."""
+        def cert(state):
+            from .solvers import solution
+            return self.certificate(solution(state), mu, gamma)
+        return cert
+
+
+class LassoPath(NamedTuple):
+    x: list               # K d-vectors in the rows' dtype, on G's device
+    certificates: list    # K CertificateResult, taken AT those (rounded) vectors
+    iterations: int       # FISTA iterations made
+    converged: list       # K booleans: the model met its gap before maxit
+
+
+def lasso_path(stats: GramStats, mus, x0=None, gap=1e-9, maxit=20000, check_every=10, dtype=None) -> LassoPath:
+    """The lasso min_x f(x) + mu_k ||x||_1 for every mu_k of `mus`, in d-space: FISTA with the step 1 / smoothness_exact(stats), all K
+    models as one d x K matrix (one d x d x K product per iteration; A is never read).  Model k stops -- its column is frozen -- at the
+    first check (every `check_every` iterations) with gap_k <= gap * max(1, objective_k), the gap being the certified duality gap of
+    certificate.assemble.  x0: None (zeros), a d-vector for all, or K of them.  Returns LassoPath: the K iterates in the rows' dtype
+    (stats.dtype; dtype= overrides), ready for solve_together and score_many, with the certificates of exactly those vectors (rounding
+    an iterate to float32 moves its gap: the certificate says what was reached, `converged` what the float64 iteration met).
+    LeastSquares statistics only."""
+    import torch
+    q = GramLasso(stats)
+    s = stats
+    mus = [float(m) for m in mus]
+    K = len(mus)
+    if K < 1 or any(not (m > 0 and math.isfinite(m)) for m in mus):
+        raise ValueError("lasso_path needs at least one l1 weight, every one > 0 and finite")
+    dev = s.G.device
+    mu = torch.tensor(mus, dtype=torch.float64, device=dev)
+    if x0 is None:
+        X = torch.zeros((s.d, K), dtype=torch.float64, device=dev)
+    elif isinstance(x0, (list, tuple)):
+        if len(x0) != K:
+            raise ValueError(f"{len(x0)} starting points for {K} models")
+        X = torch.stack([q._x(v) for v in x0], dim=1)
+    else:
+        X = q._x(x0)[:, None].repeat(1, K)
+    Lf = smoothness_exact(s)
+    if not Lf > 0:
+        raise ValueError("the Gram matrix is zero: every x minimises f")
+    step = 1.0 / Lf
+    c = s.lam / s.N
+    Y, t = X.clone(), 1.0
+    active = torch.ones(K, dtype=torch.bool, device=dev)
+    it = 0
+
+    def gaps(X):
+        grad = c * (s.G @ X - s.u[:, None])
+        Fv = q.value(X)
+        gv = mu * X.abs().sum(0)
+        ginf = grad.abs().amax(0)
+        sc = torch.where(ginf > 0, torch.clamp(mu / ginf, max=1.0), torch.ones_like(ginf))
+        dual = Fv * (2 * sc - sc * sc) - sc * (X * grad).sum(0)
+        return Fv + gv - dual, Fv + gv
+
+    while it < maxit:
+        grad = c * (s.G @ Y - s.u[:, None])
+        Xn = _soft(Y - step * grad, step * mu[None, :])
+        tn = 0.5 * (1.0 + math.sqrt(1.0 + 4.0 * t * t))
+        Yn = Xn + ((t - 1.0) / tn) * (Xn - X)
+        X = torch.where(active[None, :], Xn, X)
+        Y = torch.where(active[None, :], Yn, X)
+        t = tn
+        it += 1
+        if it % check_every == 0 or it == maxit:
+            gp, obj = gaps(X)
+            active = active & ~(gp <= gap * torch.clamp(obj, min=1.0))
+            if not bool(active.any()):
+                break
+    out_dtype = dtype or s.dtype or torch.float64
+    xs = [X[:, k].to(out_dtype).contiguous() for k in range(K)]
+    done = (~active).tolist()
+    return LassoPath(xs, [q.certificate(x, m, step) for x, m in zip(xs, mus)], it, done)

@@ -464,6 +464,17 @@ def host_col_moments(A, shift=None):
     return np.sum(t, axis=0), np.sum(t * t, axis=0)
 
 
+def host_gram(A, b):
+    """The Gram statistics of ciao_gram in numpy (float64) -> (G, u, colsum, bsum): G = A'A, u = A'b, colsum = A'1, bsum = [sum b,
+    sum b^2].  The products are what the device forms (float32 data is exact in float64, and so is every product of two of them); the
+    order of addition is numpy's, so the two agree to (N + 8) 2^-53 sum_n |a_ni a_nj| per entry, and bitwise where every sum is exact."""
+    A, b = np.asarray(A), np.asarray(b)
+    if A.ndim != 2 or np.iscomplexobj(A) or np.iscomplexobj(b) or b.shape != (A.shape[0],):
+        raise ValueError("A must be a real N x d matrix and b a real N-vector")
+    A, b = A.astype(np.float64), b.astype(np.float64)
+    return A.T @ A, A.T @ b, np.sum(A, axis=0), np.array([np.sum(b), np.sum(b * b)])
+
+
 def host_standardize(A, b=None, center=True, scale=True, refine=True):
     """standardize.standardize in numpy on a host matrix -> (A_std, b_std, mean, scale, b_mean).  The moments are
     standardize.host_column_moments' (the same shift, the same refinement rule, the same default: always refined); scale_j = 1 / sqrt(var_j) with the population variance, 1

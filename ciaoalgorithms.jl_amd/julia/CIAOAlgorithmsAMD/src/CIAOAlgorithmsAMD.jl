@@ -509,6 +509,31 @@ function standardize(F::PackedF{R}; center::Bool = true, scale::Bool = true, inp
     return Fs, (mean = center ? m.mean : zero(m.mean), scale = scale ? sc : one.(m.var), b_mean = b_mean)
 end
 
+# Gram statistics (include/ciao_hip.h: ciao_gram; Python twins: device.Context.gram, gram.gram_stats; DESIGN.md section 8.12).
+# gram: G = A'A (d x d, both triangles, the same bits: its layout does not matter), u = A'b, colsum = A'1, bsum = [Σb, Σb²], Float64
+# whatever R is (Float32 rows give the bits of their Float64 copy) -- one pass over A on the matrix cores, d <= 4096.  u / colsum / bsum
+# = false leaves that output out (NULL).  gram_stats: the named tuple gram.GramStats is, for real LeastSquares or logistic rows.
+function gram(F::PackedF{R}; u::Bool = true, colsum::Bool = true, bsum::Bool = true) where {R}
+    d = Int(F.d)
+    G = ROCArray{Float64}(undef, d, d)
+    uv = u ? ROCArray{Float64}(undef, d) : nothing
+    cs = colsum ? ROCArray{Float64}(undef, d) : nothing
+    bs = bsum ? ROCArray{Float64}(undef, 2) : nothing
+    check(ccall((:ciao_gram, libciao), Int32, (Ptr{Cvoid}, Ref{CiaoProblem}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                context().h, Ref(cproblem(F)), dptr(G), Int64(d), dptr(uv), dptr(cs), dptr(bs)))
+    return G, uv, cs, bs
+end
+
+function gram_stats(F::PackedF{R}) where {R}
+    (F.loss == LOSS_LS || F.loss == LOSS_LOGISTIC) || throw(ArgumentError("Gram statistics need real LeastSquares or logistic rows"))
+    F.N >= 1 || throw(ArgumentError("Gram statistics need at least one row"))
+    G, u, colsum, bsum = gram(F)
+    sb = Array(bsum)
+    ls = F.loss == LOSS_LS
+    return (N = Int(F.N), d = Int(F.d), G = G, u = u, colsum = colsum, sum_b = sb[1], sum_bb = sb[2], lam = ls ? Float64(F.lam) : 1.0,
+            kind = ls ? :ls : :logistic)
+end
+
 # ======================================================================================================================
 # SVRG  (src/algorithms/SVRG/SVRG.jl, SVRG_basic.jl)
 # ======================================================================================================================

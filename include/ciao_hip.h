@@ -299,6 +299,24 @@ CIAO_API int32_t ciao_col_moments(ciao_ctx *ctx, const ciao_problem *p, const do
  * row-sharded context: the local rows.  No workspace; does not synchronise. */
 CIAO_API int32_t ciao_scale_columns(ciao_ctx *ctx, const ciao_problem *p, const double *center, const double *scale, void *out,
                                     int64_t ld_out);
+/* EXTENSION beyond the reference: the second-order statistics of a packed matrix in one pass over its rows, on the matrix cores.
+ * The reference has no counterpart (its tests form A'A on the host where they need the smoothness constant).  DESIGN.md section 8.12.
+ * Over the N resident rows, for i, j < d:
+ *     G[i * ldg + j] = sum_n A[n,i] A[n,j]      u[j] = sum_n A[n,j] b_n      colsum[j] = sum_n A[n,j]
+ *     bsum[0] = sum_n b_n                       bsum[1] = sum_n b_n^2
+ * (b: the targets of CIAO_LOSS_LS rows, the labels of CIAO_LOSS_LOGISTIC rows).  G: device, d rows of stride ldg >= d DOUBLES; both
+ * triangles are written and G[i][j], G[j][i] hold the same bits; the columns [d, ldg) of a row are not written.  u, colsum: device
+ * vectors of d DOUBLES; bsum: 2 device DOUBLES; each of the three may be NULL and the others' bits do not depend on it.  Every output
+ * is double whatever p->dtype is: fp32 rows are converted to double where they become operands of v_mfma_f64_16x16x4_f64, so every
+ * product of two fp32 elements is exact, every sum is formed in double, and a matrix stored as fp32 gives the bits the same values
+ * stored as fp64 give.  One pass over A (the upper triangle of 128 x 128 tiles of G times P row partitions, then a fixed-order sum of a
+ * tile's P partial tiles), no atomics: bitwise reproducible between runs, contexts, row strides and pointer alignments -- every order of
+ * addition is a function of (N, d) alone.  Columns [d, ld) of a row are never read.  Real CIAO_LOSS_LS / CIAO_LOSS_LOGISTIC problems with
+ * d <= 4096; complex problems, CIAO_LOSS_ZERO (no A), d > 4096, ldg < d and NULL ctx / p / G are refused with CIAO_ERR_ARG and nothing is
+ * launched.  N = 0: every output is set to zero, no kernel is launched.  On a row-sharded context: the LOCAL rows only, as
+ * ciao_col_moments (the ranks' matrices are not combined).  Workspace: at most 256 MiB of partial tiles.  Does not synchronise, except
+ * where that workspace has to grow. */
+CIAO_API int32_t ciao_gram(ciao_ctx *ctx, const ciao_problem *p, double *G, int64_t ldg, double *u, double *colsum, double *bsum);
 
 /* ---- SVRG / SVRG++  (SVRG/SVRG_basic.jl) -------------------------------------------------------------------- */
 /* Base.iterate(iter), :57-66: av = full gradient at x0; z_full = x0; z = 0; w = x0. */
