@@ -17,11 +17,19 @@ from . import oracle as _O
 _F32 = np.dtype(np.float32)
 _C64 = np.dtype(np.complex64)
 _twins = {}   # id(object) -> (object, its Float64 twin): the object is kept so that an id is never reused while it is registered
+_LIMIT = 20000
 
 
 def _register(obj, twin):
-    if len(_twins) > 20000:    # a test session creates a few thousand; old entries only pin small arrays
-        _twins.clear()
+    # A session registers tens of thousands; old entries only pin small arrays.  Over the limit the OLDEST half goes (a dict keeps
+    # insertion order), never the whole registry: a test in progress would lose the twin of its Problem while its state arrays are
+    # twinned again at the next call -- the Float32 routine then ran on the Float64 copies (svrg_iterate takes its state by pointer).
+    # Assumes that no single test registers more than _LIMIT / 2 objects while its own state is live (the largest, the 1000 random
+    # chain cases, register about twenty each).
+    if len(_twins) > _LIMIT:
+        for k in list(_twins)[:_LIMIT // 2]:
+            del _twins[k]
+    _twins.pop(id(obj), None)      # registered again: the newest entry
     _twins[id(obj)] = (obj, twin)
 
 

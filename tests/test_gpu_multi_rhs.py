@@ -3,7 +3,23 @@ csrc/mrhs_kernels.h: the one place on this path where the gradients are a dense 
 
 Not in the reference, which solves one problem per call: each of the K results is held against (a) the oracle's full pass
 (SVRG_basic.jl:87-92 restated) at that iterate and (b) the library's own single sweep at that iterate -- to a stated multiple of
-eps(R) |av|_inf, not bitwise: the pass adds its rows in another order (MFMA tiles of 16 rows, partitions in order)."""
+eps(R) |av|_inf, not bitwise: the pass adds its rows in another order (MFMA tiles of 16 rows, partitions in order).
+
+What launch_mrhs plans for the eight shapes below at 256 compute units (nkb column blocks of 16 solves x P row partitions of whole 16-row
+tiles; the steady tile step needs three tiles in a partition; tests/test_multi_rhs_host.py restates the plan and asserts this table):
+
+    (d, K, N)             nkb    P   tiles per partition
+    (256, 2, 37)           1     3    1
+    (256, 16, 1000)        1    63    1
+    (512, 21, 3001)        2   128    2
+    (1024, 48, 2050)       3    80    2
+    (1024, 5, 16)          1     1    1
+    (1024, 33, 40000)      3    80   32    the only shape that stays in the steady step
+    (768, 19, 5000)        2   128    3    one steady step
+    (128, 17, 3000)        2   128    2
+
+Every d = 128, 256 and 512 shape has one or two tiles a partition: deep partitions, both block maps with several column blocks, padded
+strides, guard bands and the remaining refusals of mrhs_supported are in tests/test_gpu_multi_rhs_paths.py, exactly on integer rows."""
 import numpy as np
 import pytest
 

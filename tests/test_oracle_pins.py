@@ -345,3 +345,37 @@ def test_reference_complex_lasso_is_the_real_lasso_in_complex_containers(ctype, 
         assert xc.dtype == ctype
         assert np.array_equal(xc.real, xr) and not np.any(xc.imag), name
         assert P.lasso_cost(Ac, bc, lam, xc) - f_star < 1e-4, name
+
+
+def test_float64_twins_survive_a_full_registry(Stream):
+    """oracle.twin keeps a Float64 twin of every Float32 oracle object and drops old entries when its registry is full.  A running
+    SVRG state must keep its twins across that moment (the whole registry used to be cleared: the Problem lost its twin, and the
+    next svrg_iterate ran the Float32 routine on the Float64 copies of the state): fill the registry between two epochs and hold the
+    twinned run to a plain Float64 run on the same Float32 data."""
+    from oracle import twin as T
+    A, b, x0 = P.synthetic("logistic", 2, 5, np.float32, seed=67)
+    gamma = np.float32(0.1)
+    idx = [Stream(3).rand_indices(2, 11) for _ in range(2)]
+    saved = dict(T._twins)                             # the registry is a module global: this test works on an empty one and puts back
+    T._twins.clear()                                   # what it found, fillers gone, whatever the session holds around it
+    try:
+        filler = [np.zeros(1, np.float32) for _ in range(T._LIMIT + 30)]
+        for f in filler[:T._LIMIT - 20]:                   # every one a registration: the registry is almost full when the solve starts
+            T._up(f)
+        p, g = T.Problem("logistic", A, b, 1.0), T.Prox("l1", lam=0.02)
+        state = T.svrg_init(p, x0)
+        T.svrg_iterate(p, g, gamma, idx[0], False, *state)
+        for f in filler[T._LIMIT - 20:]:                   # ... and overflows between its two epochs
+            T._up(f)
+        assert len(T._twins) < T._LIMIT and T.twin_of(filler[0]) is None and T.twin_of(filler[-1]) is not None
+        assert T.twin_of(p) is not None and all(T.twin_of(s) is not None for s in state)
+        T.svrg_iterate(p, g, gamma, idx[1], False, *state)
+        p64, g64 = O.Problem("logistic", A.astype(np.float64), b.astype(np.float64), 1.0), O.Prox("l1", lam=0.02)
+        state64 = O.svrg_init(p64, x0.astype(np.float64))
+        for i in idx:
+            O.svrg_iterate(p64, g64, np.float64(gamma), i, False, *state64)
+        for s, s64 in zip(state, state64):
+            assert s.dtype == np.float32 and np.array_equal(T.twin_of(s), s64)
+    finally:
+        T._twins.clear()
+        T._twins.update(saved)
