@@ -15,7 +15,7 @@ int32_t launch_colmom<CIAO_T>(ciao_ctx *ctx, const ciao_problem *p, const double
     const ColsqPlan pl = colmom_plan(p->N, p->d, VEC);
     CIAO_TRY(ensure(ctx, &ctx->partial, &ctx->partial_bytes, 2 * (size_t)pl.nslab * (size_t)p->d * sizeof(double)));
     double *partial = (double *)ctx->partial;
-    const bool vec16 = (reinterpret_cast<uintptr_t>(p->A) & 15u) == 0 && ((size_t)p->ld * sizeof(T)) % 16 == 0;
+    const bool vec16 = col_vec16<T>(p->A, p->ld);
     const dim3 grid((unsigned)pl.panels, (unsigned)pl.nslab);
     if (vec16)
         hipLaunchKernelGGL((colmom_partial_kernel<T, true>), grid, dim3(COLSQ_BLOCK), 0, ctx->stream, (const T *)p->A, p->N, p->d, p->ld, pl.slab,
@@ -27,11 +27,7 @@ int32_t launch_colmom<CIAO_T>(ciao_ctx *ctx, const ciao_problem *p, const double
     hipLaunchKernelGGL((colmom_final_kernel<T>), dim3((unsigned)((p->d + COLSQ_FC - 1) / COLSQ_FC), 2), dim3(COLSQ_BLOCK), 0, ctx->stream, p->d,
                        (int)pl.nslab, (const double *)partial, s1, s2);
     CIAO_HIP(hipGetLastError());
-    char buf[160];
-    snprintf(buf, sizeof buf, "colmom_partial_kernel<%s,%s> grid=%lldx%lld block=%d tc=%d slab=%lld shift=%s", sizeof(T) == 8 ? "f64" : "f32",
-             vec16 ? "vec16" : "elem", (long long)pl.panels, (long long)pl.nslab, COLSQ_BLOCK, 1 << pl.tc_log2, (long long)pl.slab,
-             shift ? "given" : "row0");
-    ctx->last_kernel = buf;
+    ctx->last_kernel = col_report<T>("colmom_partial_kernel", vec16, pl) + (shift ? " shift=given" : " shift=row0");
     return CIAO_OK;
 }
 
@@ -42,8 +38,7 @@ int32_t launch_colscale<CIAO_T>(ciao_ctx *ctx, const ciao_problem *p, const doub
     using T = CIAO_T;
     constexpr int VEC = 16 / (int)sizeof(T);
     const ColsqPlan pl = colmom_plan(p->N, p->d, VEC);
-    const bool vec16 = (reinterpret_cast<uintptr_t>(p->A) & 15u) == 0 && ((size_t)p->ld * sizeof(T)) % 16 == 0 &&
-                       (reinterpret_cast<uintptr_t>(out) & 15u) == 0 && ((size_t)ld_out * sizeof(T)) % 16 == 0;
+    const bool vec16 = col_vec16<T>(p->A, p->ld) && col_vec16<T>(out, ld_out);
     const dim3 grid((unsigned)pl.panels, (unsigned)pl.nslab);
     if (vec16)
         hipLaunchKernelGGL((colscale_kernel<T, true>), grid, dim3(COLSQ_BLOCK), 0, ctx->stream, (const T *)p->A, p->N, p->d, p->ld, pl.slab,
@@ -52,11 +47,7 @@ int32_t launch_colscale<CIAO_T>(ciao_ctx *ctx, const ciao_problem *p, const doub
         hipLaunchKernelGGL((colscale_kernel<T, false>), grid, dim3(COLSQ_BLOCK), 0, ctx->stream, (const T *)p->A, p->N, p->d, p->ld, pl.slab,
                            pl.tc_log2, center, scale, (T *)out, ld_out);
     CIAO_HIP(hipGetLastError());
-    char buf[160];
-    snprintf(buf, sizeof buf, "colscale_kernel<%s,%s> grid=%lldx%lld block=%d tc=%d slab=%lld%s", sizeof(T) == 8 ? "f64" : "f32",
-             vec16 ? "vec16" : "elem", (long long)pl.panels, (long long)pl.nslab, COLSQ_BLOCK, 1 << pl.tc_log2, (long long)pl.slab,
-             out == p->A ? " in place" : "");
-    ctx->last_kernel = buf;
+    ctx->last_kernel = col_report<T>("colscale_kernel", vec16, pl) + (out == p->A ? " in place" : "");
     return CIAO_OK;
 }
 

@@ -16,7 +16,7 @@ int32_t launch_colsq<CIAO_T>(ciao_ctx *ctx, const ciao_problem *p, double *out)
     const ColsqPlan pl = colsq_plan(p->N, p->d, VEC);
     CIAO_TRY(ensure(ctx, &ctx->partial, &ctx->partial_bytes, (size_t)pl.nslab * (size_t)p->d * sizeof(double)));
     double *partial = (double *)ctx->partial;
-    const bool vec16 = (reinterpret_cast<uintptr_t>(p->A) & 15u) == 0 && ((size_t)p->ld * sizeof(T)) % 16 == 0;
+    const bool vec16 = col_vec16<T>(p->A, p->ld);
     const dim3 grid((unsigned)pl.panels, (unsigned)pl.nslab);
     if (vec16)
         hipLaunchKernelGGL((colsq_partial_kernel<T, true>), grid, dim3(COLSQ_BLOCK), 0, ctx->stream, (const T *)p->A, p->N, p->d, p->ld, pl.slab,
@@ -28,10 +28,7 @@ int32_t launch_colsq<CIAO_T>(ciao_ctx *ctx, const ciao_problem *p, double *out)
     hipLaunchKernelGGL((colsq_final_kernel<T>), dim3((unsigned)((p->d + COLSQ_FC - 1) / COLSQ_FC)), dim3(COLSQ_BLOCK), 0, ctx->stream, p->d,
                        (int)pl.nslab, (const double *)partial, out);
     CIAO_HIP(hipGetLastError());
-    char buf[128];
-    snprintf(buf, sizeof buf, "colsq_partial_kernel<%s,%s> grid=%lldx%lld block=%d tc=%d slab=%lld", sizeof(T) == 8 ? "f64" : "f32",
-             vec16 ? "vec16" : "elem", (long long)pl.panels, (long long)pl.nslab, COLSQ_BLOCK, 1 << pl.tc_log2, (long long)pl.slab);
-    ctx->last_kernel = buf;
+    ctx->last_kernel = col_report<T>("colsq_partial_kernel", vec16, pl);
     return CIAO_OK;
 }
 
