@@ -10,6 +10,8 @@ The directory name contains a dot, so it is loaded under the importable alias `c
     sampling.py      injected index streams (the reference's RNG draws are an explicit input here)
     solvers.py       SVRG / SAGA / SAG / Finito constructors, functors, iterator(), solution()
     parallel.py      row sharding + torch.distributed (RCCL) all-reduce hook
+    gram.py          Gram statistics (plain and with a weight per row) and what follows from them in d-space: GramLasso, lasso_path
+    newton.py        a proximal Newton path for l1-logistic rows on the weighted Gram pass (DeviceRows / HostRows)
     julia/           the Julia wrapper module (written against the same ABI; cannot run in this image)
 Importing this package does not need a GPU; creating a Context does.  There is no CPU fallback.
 """

@@ -1803,6 +1803,30 @@ int32_t ciao_gram(ciao_ctx *ctx, const ciao_problem *p, double *G, int64_t ldg, 
     return p->dtype == CIAO_F64 ? launch_gram<double>(ctx, p, G, ldg, u, colsum, bsum) : launch_gram<float>(ctx, p, G, ldg, u, colsum, bsum);
 }
 
+int32_t ciao_gram_weighted(ciao_ctx *ctx, const ciao_problem *p, const double *w, double *G, int64_t ldg, double *u, double *colsum,
+                           double *bsum)
+{
+    CIAO_REQUIRE(ctx && p && G, "ciao_gram_weighted: the context, the problem or the output matrix G is NULL");
+    CIAO_REQUIRE(w || p->N == 0, "ciao_gram_weighted: the weight vector w is NULL (ciao_gram is the unweighted call)");
+    CIAO_ENTER(ctx);
+    CIAO_TRY(check_problem(ctx, p));
+    CIAO_REQUIRE(p->loss != CIAO_LOSS_LS_COMPLEX, "ciao_gram_weighted covers real problems only (complex T: A'A of (re, im) pairs is not the Gram matrix of the complex rows)");
+    CIAO_REQUIRE(p->loss != CIAO_LOSS_ZERO, "ciao_gram_weighted needs data rows (Zero() terms have no matrix A)");
+    CIAO_REQUIRE(ldg >= p->d, "ciao_gram_weighted: the row stride of G, ldg=%lld, is below d=%lld", (long long)ldg, (long long)p->d);
+    CIAO_REQUIRE(p->d <= 4096, "ciao_gram_weighted takes rows of at most 4096 elements (got d=%lld: G alone would be %.0f MiB)", (long long)p->d,
+                 (double)p->d * (double)p->d * 8.0 / 1048576.0);
+    CIAO_REQUIRE((reinterpret_cast<uintptr_t>(w) & 7u) == 0, "ciao_gram_weighted: the weight vector w is not aligned to 8 bytes");
+    if (p->N == 0) {   // a rank that holds no row: every sum is zero, nothing is launched
+        CIAO_HIP(hipMemset2DAsync(G, (size_t)ldg * sizeof(double), 0, (size_t)p->d * sizeof(double), (size_t)p->d, ctx->stream));
+        if (u) CIAO_HIP(hipMemsetAsync(u, 0, (size_t)p->d * sizeof(double), ctx->stream));
+        if (colsum) CIAO_HIP(hipMemsetAsync(colsum, 0, (size_t)p->d * sizeof(double), ctx->stream));
+        if (bsum) CIAO_HIP(hipMemsetAsync(bsum, 0, 3 * sizeof(double), ctx->stream));
+        return CIAO_OK;
+    }
+    return p->dtype == CIAO_F64 ? launch_gram_weighted<double>(ctx, p, w, G, ldg, u, colsum, bsum)
+                                : launch_gram_weighted<float>(ctx, p, w, G, ldg, u, colsum, bsum);
+}
+
 int32_t ciao_screen(ciao_ctx *ctx, int32_t dtype, int64_t d, const void *grad, const double *colsq, double s, double kappa, double mu,
                     uint8_t *keep, int64_t *n_kept_host)
 {

@@ -29,6 +29,10 @@
 // Order of addition.  An element of a record: the rows of the partition in groups of four, each group by one MFMA onto the running sum;
 // then the P records in partition order.  A function of (N, d) alone: not of ld, of the base, of the rows' type (fp32 values are exact in
 // double and so is every product of two of them), of the NULL outputs, or of the run.
+//
+// With a weight per row (ciao_gram_weighted): gram_partial_kernel<Weighted<T>> and gram_final_kernel<Weighted<T>>,
+// the same kernel text instantiated on a tag type -- see Weighted<T> below.  G = A' diag(w) A, u = A'(w b), colsum = A'w,
+// bsum = {sum w b, sum w b^2, sum w}; plan, tile map, workspace and order of addition are the ones above.
 #pragma once
 
 #include "ciao_common.h"
@@ -42,7 +46,7 @@ constexpr int GRAM_PITCH = GRAM_T + 16;     // LDS row in doubles: consecutive r
 constexpr int GRAM_OFF_U = GRAM_T * GRAM_T;          // a record: the tile, then u, colsum (128 each), then {sum b, sum b^2}
 constexpr int GRAM_OFF_CS = GRAM_OFF_U + GRAM_T;
 constexpr int GRAM_OFF_B = GRAM_OFF_CS + GRAM_T;
-constexpr int GRAM_REC = GRAM_OFF_B + 8;             // doubles per (tile, partition) record
+constexpr int GRAM_REC = GRAM_OFF_B + 8;             // doubles per (tile, partition) record (weighted: a third sum, sum w, at GRAM_OFF_B + 2)
 constexpr int GRAM_WG_TARGET = 2048;        // workgroups asked for (8 per CU, as colsq / rowsq / mscore)
 constexpr size_t GRAM_WS_BYTES = (size_t)256 << 20;
 constexpr int GRAM_MAX_D = 4096;
@@ -106,9 +110,42 @@ struct GramArgs {
 
 constexpr size_t gram_lds_bytes() { return (size_t)2 * 2 * GRAM_KC * GRAM_PITCH * sizeof(double); }
 
+// The weighted instantiation (ciao_gram_weighted): gram_partial_kernel<Weighted<T>> is the same kernel text with
+// a weight per row, a.w = N doubles; gram_partial_kernel<T> compiles to what it was without it.  Exactly ONE operand of every MFMA
+// carries the weight, multiplied in double with one rounding where the operand is made; the other operand is the raw element:
+//     - panel J is parked in LDS already weighted (w_n a_nj); on a diagonal tile panel I is parked twice, raw into its own slot and weighted
+//       into the J slot a diagonal tile otherwise leaves unused, so every wave reads raw I against weighted J and the MFMA loop is the
+//       unweighted one;
+//     - the augmented wave keeps a raw [b, 1] and a weighted [w b, w] operand: u, colsum from the panel against the weighted one, and raw
+//       against weighted gives sum w b^2 (0, 0), sum w b (0, 1) and sum w (1, 1).
+// The thread that parks a chunk of a row fetches that row's weight with the chunk (NLD rows a thread and chunk), at a row index CLAMPED
+// into the partition (min(row, r_hi - 1)): nothing beyond w[N - 1] is read, the load has no branch of its own, and its value is first
+// used at the parking, after the MFMA loop.  A row that does not exist therefore carries the weight of the partition's last row against
+// elements that are 0 in both operands: the products are the zeros a weight of 0 would give, for every finite weight (and a non-finite
+// weight of an existing row makes every output NaN whichever way).  With w = 1 every operand is the unweighted one (1 a is exact) and the
+// order of addition is the same: the same bits.
 template <typename T>
-__global__ void __launch_bounds__(GRAM_BLOCK) gram_partial_kernel(GramArgs<T> a)
+struct Weighted {};
+template <typename TT>
+struct GramElem {
+    using type = TT;
+    static constexpr bool weighted = false;
+};
+template <typename T>
+struct GramElem<Weighted<T>> {
+    using type = T;
+    static constexpr bool weighted = true;
+};
+template <typename T>
+struct GramArgs<Weighted<T>> : GramArgs<T> {
+    const double *w;   // N doubles, 8-byte aligned
+};
+
+template <typename TT>
+__global__ void __launch_bounds__(GRAM_BLOCK) gram_partial_kernel(GramArgs<TT> a)
 {
+    using T = typename GramElem<TT>::type;
+    constexpr bool WEIGHTED = GramElem<TT>::weighted;
     using M = MfmaOf<double>;
     using Acc = typename M::acc;
     constexpr int VEC = 16 / (int)sizeof(T);
@@ -185,12 +222,46 @@ __global__ void __launch_bounds__(GRAM_BLOCK) gram_partial_kernel(GramArgs<T> a)
             }
         }
     };
+    // (WEIGHTED) the weights of the rows this thread parks, staged with the panels, and the weighted parking: w_n a, one rounding
+    double wst[NLD] = {};
+    auto load_weights = [&](int64_t t0) {
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            // (no branch around the load and no use of its value before the parking: either would make the wave wait for the chunk's
+            // loads BEFORE its MFMA loop.  The index is clamped into the partition, so nothing beyond w[N - 1] is read; a row that does not
+            // exist meets elements that are 0 in both operands, and 0 times a finite weight is the 0 a weight of 0 gives.)
+            const int64_t row = t0 + (i * GRAM_BLOCK + tid) / CPR;
+            if constexpr (WEIGHTED) wst[i] = a.w[row < r_hi ? row : r_hi - 1];
+        }
+    };
+    auto park_weighted = [&](const Vld(&st)[NLD], double *dst) {
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            const int q = i * GRAM_BLOCK + tid;
+            double *o = dst + (q / CPR) * GRAM_PITCH + (q % CPR) * VEC;
+#pragma unroll
+            for (int e = 0; e < VEC; e += 2) {
+                D2 v;
+                v[0] = wst[i] * (double)st[i][e];
+                v[1] = wst[i] * (double)st[i][e + 1];
+                *reinterpret_cast<D2 *>(o + e) = v;
+            }
+        }
+    };
     // the augmented B operand of a chunk, lane (column c, slot h), step ks: row t0 + 4 ks + h of [b, 1, 0 ... 0]; 0 where the row does not exist
+    // (WEIGHTED: and its weighted twin [w b, w, 0 ... 0])
     double augn[GRAM_KC / 4] = {}, aug[GRAM_KC / 4];
+    double augwn[GRAM_KC / 4] = {}, augw[GRAM_KC / 4] = {};
     auto load_aug = [&](int64_t t0) {
 #pragma unroll
         for (int ks = 0; ks < GRAM_KC / 4; ++ks) {
             const int64_t row = t0 + 4 * ks + h;
+            if constexpr (WEIGHTED) {   // the raw b_n and w_n by loads without branches (clamped index); the operands are made where they are used
+                const int64_t rc = row < r_hi ? row : r_hi - 1;
+                augn[ks] = (double)a.b[rc];
+                augwn[ks] = a.w[rc];
+                continue;
+            }
             double v = 0.0;
             if (row < r_hi) {
                 if (c == 0) v = (double)a.b[row];
@@ -205,25 +276,42 @@ __global__ void __launch_bounds__(GRAM_BLOCK) gram_partial_kernel(GramArgs<T> a)
     for (int i = 0; i < 16; ++i) acc[i] = Acc(0.0);
 
     if (r_lo < r_hi) {
+        if constexpr (WEIGHTED) load_weights(r_lo);
         load_panel(stI, ci0, r_lo);
         if (!diag) load_panel(stJ, cj0, r_lo);
         if (augwave) load_aug(r_lo);
         park_panel(stI, lds);
-        if (!diag) park_panel(stJ, lds + PANEL);
+        if constexpr (WEIGHTED) {
+            if (diag)
+                park_weighted(stI, lds + PANEL);
+            else
+                park_weighted(stJ, lds + PANEL);
+        } else {
+            if (!diag) park_panel(stJ, lds + PANEL);
+        }
     }
     __syncthreads();
     int buf = 0;
     for (int64_t t0 = r_lo; t0 < r_hi; t0 += GRAM_KC) {   // (uniform in the workgroup)
         const bool next = t0 + GRAM_KC < r_hi;
 #pragma unroll
-        for (int ks = 0; ks < GRAM_KC / 4; ++ks) aug[ks] = augn[ks];
+        for (int ks = 0; ks < GRAM_KC / 4; ++ks) {
+            if constexpr (WEIGHTED) {   // [b, 1, 0 ... 0] and [w b, w, 0 ... 0] of row t0 + 4 ks + h from the raw loads of a chunk ago; 0 where the row does not exist
+                const bool have = augwave && t0 + 4 * ks + h < r_hi;
+                aug[ks] = have ? (c == 0 ? augn[ks] : c == 1 ? 1.0 : 0.0) : 0.0;
+                augw[ks] = have && c < 2 ? augwn[ks] * aug[ks] : 0.0;
+            } else {
+                aug[ks] = augn[ks];
+            }
+        }
         if (next) {
+            if constexpr (WEIGHTED) load_weights(t0 + GRAM_KC);
             load_panel(stI, ci0, t0 + GRAM_KC);
             if (!diag) load_panel(stJ, cj0, t0 + GRAM_KC);
             if (augwave) load_aug(t0 + GRAM_KC);
         }
         const double *sI = lds + (size_t)buf * 2 * PANEL;
-        const double *sJ = diag ? sI : sI + PANEL;
+        const double *sJ = (!WEIGHTED && diag) ? sI : sI + PANEL;
         if (!augwave) {
             const double *pI = sI + h * GRAM_PITCH + wi * 64 + c;
             const double *pJ = sJ + h * GRAM_PITCH + wj * 64 + c;
@@ -248,14 +336,21 @@ __global__ void __launch_bounds__(GRAM_BLOCK) gram_partial_kernel(GramArgs<T> a)
 #pragma unroll
                 for (int s = 0; s < 8; ++s) av[s] = pI[ks * 4 * GRAM_PITCH + s * 16];
 #pragma unroll
-                for (int s = 0; s < 8; ++s) acc[s] = M::mma(av[s], aug[ks], acc[s]);
-                acc[8] = M::mma(aug[ks], aug[ks], acc[8]);
+                for (int s = 0; s < 8; ++s) acc[s] = M::mma(av[s], WEIGHTED ? augw[ks] : aug[ks], acc[s]);
+                acc[8] = M::mma(aug[ks], WEIGHTED ? augw[ks] : aug[ks], acc[8]);
             }
         }
         if (next) {
             double *dst = lds + (size_t)(buf ^ 1) * 2 * PANEL;
             park_panel(stI, dst);
-            if (!diag) park_panel(stJ, dst + PANEL);
+            if constexpr (WEIGHTED) {
+                if (diag)
+                    park_weighted(stI, dst + PANEL);
+                else
+                    park_weighted(stJ, dst + PANEL);
+            } else {
+                if (!diag) park_panel(stJ, dst + PANEL);
+            }
         }
         __syncthreads();
         buf ^= 1;
@@ -280,18 +375,21 @@ __global__ void __launch_bounds__(GRAM_BLOCK) gram_partial_kernel(GramArgs<T> a)
                 for (int q = 0; q < 4; ++q) o[s * 16 + M::row(h, q)] = acc[s][q];
             // [b, 1]'[b, 1]: row 0 (h = 0, q = 0), column 0: sum b^2; column 1: sum b
             if (h == 0) rec[GRAM_OFF_B + (c == 0 ? 1 : 0)] = acc[8][0];
+            // (WEIGHTED) [b, 1]'[w b, w]: row 1 (h = 1, q = 0), column 1: sum w
+            if (WEIGHTED && h == 1 && c == 1) rec[GRAM_OFF_B + 2] = acc[8][0];
         }
     }
 }
 
 // Workgroups [0, 64 ntiles): 256 elements of a tile each, thread = element (i, j): the P records in partition order, then G[i][j] and
 // its mirror from the same sum.  Workgroups [64 ntiles, 64 ntiles + nb): u (threads 0 .. 127) and colsum (128 .. 255) of a column block, from
-// the records of its diagonal tile.  The last workgroup: bsum, from the records of tile 0.  NULL outputs are skipped.  (T only keeps the two
-// units' copies apart.)
-template <typename T>
+// the records of its diagonal tile.  The last workgroup: bsum, from the records of tile 0 (Weighted<T>: three sums).  NULL outputs are skipped.
+// (T only keeps the two units' copies apart.)
+template <typename TT>
 __global__ void __launch_bounds__(GRAM_BLOCK) gram_final_kernel(int64_t d, int nb, int ntiles, int P, const double *rec, double *G, int64_t ldg,
                                                                  double *u, double *colsum, double *bsum)
 {
+    constexpr int NBSUM = GramElem<TT>::weighted ? 3 : 2;   // the weighted statistics: a third slot, sum w
     const int blk = blockIdx.x, tid = threadIdx.x;
     if (blk < ntiles * GRAM_FINAL_BLOCKS) {
         const int t = blk / GRAM_FINAL_BLOCKS, e = (blk % GRAM_FINAL_BLOCKS) * GRAM_BLOCK + tid;
@@ -314,7 +412,7 @@ __global__ void __launch_bounds__(GRAM_BLOCK) gram_final_kernel(int64_t d, int n
         double s = 0.0;
         for (int p = 0; p < P; ++p) s += q[(size_t)p * GRAM_REC];
         out[col] = s;
-    } else if (bsum && tid < 2) {
+    } else if (bsum && tid < NBSUM) {
         const double *q = rec + GRAM_OFF_B + tid;
         double s = 0.0;
         for (int p = 0; p < P; ++p) s += q[(size_t)p * GRAM_REC];

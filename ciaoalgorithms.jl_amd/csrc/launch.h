@@ -179,6 +179,10 @@ int32_t launch_colscale(ciao_ctx *ctx, const ciao_problem *p, const double *cent
 // gram_plan(N, d) go to ctx->partial (grown here).  Specialised in gram_f32.hip / gram_f64.hip.
 template <typename T>
 int32_t launch_gram(ciao_ctx *ctx, const ciao_problem *p, double *G, int64_t ldg, double *u, double *colsum, double *bsum);
+// ... with a weight per row (w: N device doubles, not NULL): A' diag(w) A and the weighted sums; bsum = {sum w b, sum w b^2, sum w}
+template <typename T>
+int32_t launch_gram_weighted(ciao_ctx *ctx, const ciao_problem *p, const double *w, double *G, int64_t ldg, double *u, double *colsum,
+                             double *bsum);
 
 // ProShI agent rows (init or one batch) + finalize + epilogue.  Specialised in rows_f32.hip / rows_f64.hip.
 template <typename T>

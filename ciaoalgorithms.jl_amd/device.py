@@ -599,18 +599,29 @@ class Context:
         return out
 
     # -- Gram statistics (gram.py) -------------------------------------------------------------------
-    def gram(self, F, G=None, u=True, colsum=True, bsum=True):
+    def gram(self, F, G=None, u=True, colsum=True, bsum=True, weights=None):
         """(G, u, colsum, bsum) with G = A'A (d x d), u = A'b, colsum = A'1 and bsum = (sum b, sum b^2) over the N local rows of F
         (include/ciao_hip.h: ciao_gram) -> device float64 tensors whatever F's dtype is; fp32 rows give the bits their .double() copy
         gives.  G: a row-major float64 device matrix of d rows (any row stride >= d; columns beyond d are not written), a fresh one by
         default; both triangles are written with the same bits.  u / colsum / bsum: a float64 device vector (d, d, 2 elements) to write
         into, True for a fresh one, or None / False to leave it out (NULL: the others' bits do not change).  One pass over A on the
         matrix cores, paid once per dataset; bitwise reproducible.  d <= 4096.  Does not synchronise, except where the workspace of
-        partial tiles has to grow."""
+        partial tiles has to grow.
+
+        weights: a contiguous float64 device N-vector w, one weight per local row (include/ciao_hip.h: ciao_gram_weighted; DESIGN.md
+        section 8.13) -> G = A'diag(w)A, u = A'(w b), colsum = A'w and bsum = (sum w b, sum w b^2, sum w): THREE elements then.  One
+        operand of every product is w_n times an element, rounded once, the other the raw element: any finite weight, negative ones
+        included; w = 1 gives the unweighted bits; 0/1 weights the statistics of a row subset.  A zero weight does not mask a
+        non-finite element (0 inf = NaN)."""
         if isinstance(F, PackedSepQuad):
             raise L.CiaoError(L.ERR_ARG, "the Gram matrix exists for LeastSquares / logistic rows, not for the sharing problem")
         dev = f"cuda:{self.device}"
         d = F.d
+        if weights is not None and not (isinstance(weights, torch.Tensor) and weights.is_cuda and weights.device.index == self.device
+                                        and weights.dtype == torch.float64 and weights.dim() == 1 and weights.shape[0] == F.N
+                                        and weights.is_contiguous()):
+            raise ValueError(f"weights: need a contiguous float64 vector of {F.N} elements on cuda:{self.device}")
+        nb = 2 if weights is None else 3
 
         def fresh(*shape):
             t = torch.empty(shape, dtype=torch.float64, device=dev)
@@ -625,7 +636,7 @@ class Context:
             raise ValueError(f"G: need a row-major float64 device matrix of shape ({d}, {d})")
         ldg = int(G.stride(0)) if d > 1 else d
         outs = []
-        for v, name, n in ((u, "u", d), (colsum, "colsum", d), (bsum, "bsum", 2)):
+        for v, name, n in ((u, "u", d), (colsum, "colsum", d), (bsum, "bsum", nb)):
             if v is None or v is False:
                 outs.append(None)
             elif v is True:
@@ -633,7 +644,11 @@ class Context:
             else:
                 self._dvec(v, name, n)
                 outs.append(v)
-        L.check(self.lib.ciao_gram(self._h, F.ref, _ptr(G), ldg, *(None if v is None else _ptr(v) for v in outs)))
+        outp = [None if v is None else _ptr(v) for v in outs]
+        if weights is None:
+            L.check(self.lib.ciao_gram(self._h, F.ref, _ptr(G), ldg, *outp))
+        else:
+            L.check(self.lib.ciao_gram_weighted(self._h, F.ref, _ptr(weights), _ptr(G), ldg, *outp))
         return (G, *outs)
 
     # -- SVRG ------------------------------------------------------------------------------------------------------------

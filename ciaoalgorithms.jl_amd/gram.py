@@ -36,6 +36,7 @@ class GramStats(NamedTuple):
     lam: float        # LeastSquares(a, b, lam)'s lam; 1.0 for logistic rows
     kind: str         # "ls" or "logistic"
     dtype: object = None   # the dtype of the rows the statistics came from (lasso_path returns iterates in it); None: float64
+    sum_w: float = None    # weighted statistics (gram_stats(weights=)): sum of the weights; None: unweighted, to be read as N
 
     def to(self, device):
         """The same statistics with their tensors on another device."""
@@ -53,9 +54,16 @@ class GramStats(NamedTuple):
         the factor by which the subtraction G_jj - N mean_j^2 magnifies G's own rounding.  A column whose mean is a
         thousand standard deviations loses twenty bits here.  Where the amplification of some column exceeds 2^10
         (AMPLIFICATION_LIMIT, the rule of section 8.10), standardise the matrix itself -- standardize.standardize, which subtracts the
-        mean from every entry before anything is squared -- and take gram_stats of the result."""
+        mean from every entry before anything is squared -- and take gram_stats of the result.
+
+        Weighted statistics (sum_w is not None) are REFUSED: weighted column moments would divide by sum w where N stands here, and
+        with weights of both signs that variance has no sign; standardise the matrix itself (standardize.standardize), or take the
+        statistics of the standardised rows with the same weights."""
         import torch
         from .standardize import Scaler
+        if self.sum_w is not None:
+            raise L.CiaoError(L.ERR_ARG, "standardized() is defined for unweighted statistics only: these carry a weight per row "
+                                         "(sum_w is set); standardise the matrix itself and take its weighted statistics")
         n = float(self.N)
         G, u = self.G, self.u
         mean = self.colsum / n
@@ -81,10 +89,16 @@ class GramStats(NamedTuple):
         return self._replace(G=G, u=sc * u, colsum=sc * colsum, sum_b=sum_b, sum_bb=sum_bb), scaler
 
 
-def gram_stats(ctx, F) -> GramStats:
+def gram_stats(ctx, F, weights=None) -> GramStats:
     """One pass over the rows of F (Context.gram) -> GramStats on F's device.  F: a device.PackedF of real LeastSquares or logistic rows
     with d <= 4096; refused on a row-sharded context (the ranks' matrices would have to be added).  Synchronises (the two sums of b
-    cross to the host)."""
+    cross to the host).
+
+    weights: a float64 device N-vector w (Context.gram(weights=)) -> the weighted statistics: G = A'diag(w)A,
+    u = A'(w b), colsum = A'w, sum_b = sum w b, sum_bb = sum w b^2, sum_w = sum w.  N stays the row count, so the objective GramLasso
+    evaluates is lam / (2 N) sum_i w_i (a_i'x - b_i)^2; GramLasso, lasso_path and mu_max take such statistics as they are (sample
+    weights; with 0/1 weights a fold of a cross-validation without copying rows).  Weights of both signs are summed faithfully, but the
+    lasso functions assume G positive semidefinite."""
     from .device import PackedF
     from .stepsize import _on_stream
     if not isinstance(F, PackedF) or F.loss not in (L.LOSS_LS, L.LOSS_LOGISTIC):
@@ -95,26 +109,26 @@ def gram_stats(ctx, F) -> GramStats:
                                      "Gram matrices are not combined")
     if F.N < 1:
         raise L.CiaoError(L.ERR_ARG, "gram_stats needs at least one row (N = 0)")
-    G, u, colsum, bsum = ctx.gram(F)
+    G, u, colsum, bsum = ctx.gram(F, weights=weights)
     with _on_stream(ctx):
         sb = bsum.cpu()
     ls = F.loss == L.LOSS_LS
     return GramStats(int(F.N), int(F.d), G, u, colsum, float(sb[0]), float(sb[1]), float(F.lam) if ls else 1.0, "ls" if ls else "logistic",
-                     F.dtype)
+                     F.dtype, None if weights is None else float(sb[2]))
 
 
-def host_gram_stats(A, b, lam=1.0, kind="ls") -> GramStats:
-    """GramStats from host_route.host_gram on a host matrix (numpy), as CPU torch tensors."""
+def host_gram_stats(A, b, lam=1.0, kind="ls", weights=None) -> GramStats:
+    """GramStats from host_route.host_gram on a host matrix (numpy), as CPU torch tensors.  weights: a real N-vector (gram_stats)."""
     import numpy as np
     import torch
     from .host_route import host_gram
     if kind not in ("ls", "logistic"):
         raise ValueError(f"kind must be 'ls' or 'logistic' (got {kind!r})")
     A = np.asarray(A)
-    G, u, colsum, bsum = host_gram(A, b)
+    G, u, colsum, bsum = host_gram(A, b, weights)
     dt = torch.float32 if A.dtype == np.float32 else torch.float64
     return GramStats(A.shape[0], A.shape[1], torch.from_numpy(G), torch.from_numpy(u), torch.from_numpy(colsum), float(bsum[0]), float(bsum[1]),
-                     float(lam) if kind == "ls" else 1.0, kind, dt)
+                     float(lam) if kind == "ls" else 1.0, kind, dt, None if weights is None else float(bsum[2]))
 
 
 def smoothness_exact(stats: GramStats) -> float:
@@ -135,7 +149,7 @@ def mu_max(stats: GramStats) -> float:
 def _need_ls(stats, what):
     if stats.kind != "ls":
         raise L.CiaoError(L.ERR_ARG, f"{what} needs the statistics of LeastSquares rows: the logistic loss is not a function of A'A and A'b "
-                                     "(a Gram route for logistic solves is not built)")
+                                     "(newton.logistic_newton is the Gram route for logistic rows)")
 
 
 def _soft(v, tau):

@@ -464,15 +464,30 @@ def host_col_moments(A, shift=None):
     return np.sum(t, axis=0), np.sum(t * t, axis=0)
 
 
-def host_gram(A, b):
+def host_gram(A, b, weights=None):
     """The Gram statistics of ciao_gram in numpy (float64) -> (G, u, colsum, bsum): G = A'A, u = A'b, colsum = A'1, bsum = [sum b,
     sum b^2].  The products are what the device forms (float32 data is exact in float64, and so is every product of two of them); the
-    order of addition is numpy's, so the two agree to (N + 8) 2^-53 sum_n |a_ni a_nj| per entry, and bitwise where every sum is exact."""
+    order of addition is numpy's, so the two agree to (N + 8) 2^-53 sum_n |a_ni a_nj| per entry, and bitwise where every sum is exact.
+
+    weights: a real N-vector w (ciao_gram_weighted) -> G = A'diag(w)A, u = A'(w b), colsum = A'w, bsum = [sum w b, sum w b^2, sum w].
+    As on the device ONE operand of every product carries the weight, rounded once: G[i][j] = sum_n a_ni (w_n a_nj) for i <= j and the
+    other triangle is its mirror; u[j] = sum_n a_nj (w_n b_n); colsum[j] = sum_n a_nj w_n; sum w b^2 = sum_n b_n (w_n b_n).  No square
+    root of w: any finite weight, w = 1 gives the unweighted result bit for bit, a zero weight does not mask a non-finite element.
+    The bound grows to (N + 10) 2^-53 sum_n |w_n a_ni a_nj|."""
     A, b = np.asarray(A), np.asarray(b)
     if A.ndim != 2 or np.iscomplexobj(A) or np.iscomplexobj(b) or b.shape != (A.shape[0],):
         raise ValueError("A must be a real N x d matrix and b a real N-vector")
     A, b = A.astype(np.float64), b.astype(np.float64)
-    return A.T @ A, A.T @ b, np.sum(A, axis=0), np.array([np.sum(b), np.sum(b * b)])
+    if weights is None:
+        return A.T @ A, A.T @ b, np.sum(A, axis=0), np.array([np.sum(b), np.sum(b * b)])
+    w = np.asarray(weights)
+    if np.iscomplexobj(w) or w.shape != (A.shape[0],):
+        raise ValueError("weights must be a real N-vector")
+    w = w.astype(np.float64)
+    WA, wb = w[:, None] * A, w * b
+    G = np.triu(A.T @ WA)
+    G = G + np.triu(G, 1).T
+    return G, A.T @ wb, A.T @ w, np.array([np.sum(wb), b @ wb, np.sum(w)])
 
 
 def host_standardize(A, b=None, center=True, scale=True, refine=True):

@@ -524,6 +524,21 @@ function gram(F::PackedF{R}; u::Bool = true, colsum::Bool = true, bsum::Bool = t
     return G, uv, cs, bs
 end
 
+# gram_weighted: the same with a weight per row (ciao_gram_weighted; Python twin: Context.gram(weights=); DESIGN.md section 8.13):
+# G = A'diag(w)A, u = A'(w b), colsum = A'w, bsum = [Σwb, Σwb², Σw].  w: N Float64 on the device.  One operand of every product is
+# w_n times an element, rounded once, the other the raw element: any finite weight, w = 1 gives gram's bits, 0/1 weights a row subset.
+function gram_weighted(F::PackedF{R}, w::ROCArray{Float64}; u::Bool = true, colsum::Bool = true, bsum::Bool = true) where {R}
+    length(w) == F.N || throw(ArgumentError("gram_weighted needs one weight per row"))
+    d = Int(F.d)
+    G = ROCArray{Float64}(undef, d, d)
+    uv = u ? ROCArray{Float64}(undef, d) : nothing
+    cs = colsum ? ROCArray{Float64}(undef, d) : nothing
+    bs = bsum ? ROCArray{Float64}(undef, 3) : nothing
+    check(ccall((:ciao_gram_weighted, libciao), Int32, (Ptr{Cvoid}, Ref{CiaoProblem}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                context().h, Ref(cproblem(F)), dptr(w), dptr(G), Int64(d), dptr(uv), dptr(cs), dptr(bs)))
+    return G, uv, cs, bs
+end
+
 function gram_stats(F::PackedF{R}) where {R}
     (F.loss == LOSS_LS || F.loss == LOSS_LOGISTIC) || throw(ArgumentError("Gram statistics need real LeastSquares or logistic rows"))
     F.N >= 1 || throw(ArgumentError("Gram statistics need at least one row"))

@@ -1,0 +1,290 @@
+"""A proximal Newton method for l1-regularised logistic rows with N >> d, on the weighted Gram pass.
+
+    minimise  Phi(x) = (1/N) sum_i log(1 + exp(-y_i a_i'x)) + mu ||x||_1
+
+One outer iteration, everything in double:
+
+    t = y o (A x)      p = sigma(-t)      w = p (1 - p)                  N-vector torch ops (numpy on the host): off the hot path
+    H = A' diag(w) A / N                                                  ONE weighted Gram pass (ciao_gram_weighted)
+    u = (N H) x - N grad f(x)                                             grad f from the existing full-gradient pass: no division by w,
+                                                                          so saturated samples (w = 0) are harmless
+    x^ = argmin_z (1/2N)(z'(N H) z - 2 u'z) + mu ||z||_1                  gram.lasso_path on GramStats(G = N H, u), warm-started at x, to
+                                                                          a gap INNER_FACTOR below the outer one: d-space, A is not read
+    Delta = x^ - x;  backtracking: the first s in 1, 1/2, 1/4 ... with
+        Phi(x + s Delta) <= Phi(x) + 1e-4 s (grad f'Delta + mu ||x^||_1 - mu ||x||_1)        (Lee, Sun, Saunders 2014)
+                                                                          one row_dots pass + one margin_stats reduction per trial
+
+and stops when the logistic duality gap of section 8.7 is <= gap * max(1, objective) (converged), when the line search finds no
+decrease -- no trial passes the test, or the accepted one lowered Phi by less than Phi resolves in the rows' precision (RESOLUTION)
+without halving the gap either -- (converged = False, reason = "stalled": float32 rows end this way once the gap sits at the noise of
+float32 dots; so does a solve whose own evaluation of the gap meets the bound while the returned certificate, another order of
+addition over the same vector, does not), or after max_outer iterations (reason = "max_outer").  Per outer iteration: one weighted Gram pass, one full-gradient pass and one row-dots
+pass per line-search trial (the accepted trial's dots are the next iteration's); one certificate pass at the end.
+
+`rows` is a small protocol (vector, as64, dots, loss, gradient, hessian, certificate, stream) with two implementations: DeviceRows(ctx, F) -- Context.full_gradient, row_dots, margin_stats,
+certificate(samples=True) and gram(weights=) -- and HostRows(A, y) -- numpy and host_route -- so that the driver runs end to end
+without a GPU.  solvers.py imports nothing of this module.
+"""
+from __future__ import annotations
+
+import math
+from typing import NamedTuple
+
+from . import _lib as L
+from .certificate import CertificateResult, assemble
+from .gram import GramStats, lasso_path
+
+INNER_FACTOR = 0.1        # the subproblem is solved to INNER_FACTOR * gap (relative to max(1, model value), as lasso_path measures it)
+ARMIJO = 1e-4
+MAX_HALVINGS = 30
+RESOLUTION = 8.0          # a decrease of Phi below RESOLUTION * eps(rows' dtype) * max(1, Phi) cannot be told from the rounding of the row
+                          # dots Phi is evaluated from.  Such a step still counts while it halves the duality gap (the last steps of a
+                          # float64 solve do: the gap is first-order in the distance, Phi second-order); one that does neither is no
+                          # decrease the line search found, and the solve has stalled
+HOST_SUBPROBLEM_D = 2048  # up to this d the d x d subproblem is solved on the host (thousands of tiny products: launch-bound on a GPU)
+
+
+class Passes(NamedTuple):
+    gram: int          # weighted Gram passes (N d^2 flops each)
+    first_order: int   # full-gradient, row-dots and certificate passes (N d elements read each)
+
+
+class NewtonResult(NamedTuple):
+    x: object                       # the iterate, in the rows' own form: a device d-vector of F's dtype / a numpy d-vector of A's dtype
+    certificate: CertificateResult  # rows.certificate at exactly that vector
+    outer: int                      # outer iterations made (weighted Gram passes)
+    passes: Passes
+    converged: bool                 # certificate.gap <= gap * max(1, certificate.objective)
+    reason: str                     # "gap", "stalled" or "max_outer"
+
+
+def _sigmoid_weights(t):
+    """w = sigma(-t) (1 - sigma(-t)) without overflow, for a float64 torch vector t"""
+    import torch
+    e = torch.exp(-t.abs())
+    return e / ((1.0 + e) * (1.0 + e))
+
+
+class DeviceRows:
+    """Logistic rows packed for the device: F = device.PackedF.logistic(A, y) on ctx (float32 or float64 rows, d <= 4096); refused on
+    a row-sharded context."""
+
+    def __init__(self, ctx, F):
+        from .device import PackedF
+        if not isinstance(F, PackedF) or F.loss != L.LOSS_LOGISTIC:
+            raise L.CiaoError(L.ERR_ARG, "DeviceRows takes a device.PackedF of logistic rows (PackedF.logistic)")
+        if ctx.is_row_sharded() or F.N_total != F.N:
+            raise L.CiaoError(L.ERR_ARG, "DeviceRows on a row-sharded context: the ranks' weighted Gram matrices are not combined")
+        if F.N < 1:
+            raise L.CiaoError(L.ERR_ARG, "DeviceRows needs at least one row (N = 0)")
+        self.ctx, self.F = ctx, F
+        self.N, self.d, self.dtype, self.device = int(F.N), int(F.d), F.dtype, F.A.device
+
+    def stream(self):
+        """torch's own operations on these rows' vectors run inside this: on the context's stream, behind the kernels that produced
+        their inputs and ahead of the kernels that read their results (a Context made on a stream of its own is not torch's current
+        stream).  Every method below enters it itself; the driver keeps it for its whole iteration."""
+        import torch
+        from .stepsize import _on_stream
+        if self.ctx.stream is not None and torch.cuda.current_stream(self.device) != self.ctx.stream:
+            self.ctx.stream.wait_stream(torch.cuda.current_stream(self.device))   # what the caller queued (an x0) comes first
+        return _on_stream(self.ctx)
+
+    def vector(self, x64):
+        with self.stream():
+            return x64.to(device=self.device, dtype=self.dtype).contiguous()
+
+    def as64(self, x):
+        import torch
+        with self.stream():
+            return torch.as_tensor(x).to(device=self.device, dtype=torch.float64)
+
+    def dots(self, x):
+        return self.ctx.row_dots(self.F, x)
+
+    def loss(self, dots, s=1.0):
+        st = self.ctx.margin_stats(self.F, dots, s)
+        return st.loss_sum / self.N, st.entropy
+
+    def gradient(self, x):
+        import torch
+        with self.stream():                    # (av is allocated on the stream that writes and reads it)
+            av = torch.empty_like(x)
+            self.ctx.full_gradient(self.F, x, av)
+            return av.double()
+
+    def hessian(self, dots):
+        with self.stream():
+            w = _sigmoid_weights(self.F.b.double() * dots.double())
+            return self.ctx.gram(self.F, u=None, colsum=None, bsum=None, weights=w)[0]
+
+    def certificate(self, x, mu, gamma):
+        from .device import ProxG
+        return self.ctx.certificate(self.F, ProxG(L.PROX_L1, lam=mu), x, gamma, samples=True)
+
+
+class HostRows:
+    """The same rows on the host: A a real N x d numpy matrix (float32 or float64), y its N labels (+-1).  Row dots and the gradient
+    are formed in A's dtype, as the device forms them; the statistics and the weighted Gram matrix (host_route.host_gram) in double."""
+
+    def __init__(self, A, y):
+        import numpy as np
+        import torch
+        A, y = np.asarray(A), np.asarray(y)
+        if A.ndim != 2 or A.dtype not in (np.float32, np.float64) or y.shape != (A.shape[0],) or A.shape[0] < 1:
+            raise ValueError("HostRows: A must be a float32 / float64 N x d matrix with N >= 1 and y an N-vector")
+        self.A, self.y = A, y.astype(A.dtype)
+        self.N, self.d = A.shape
+        self.dtype, self.device = (torch.float32 if A.dtype == np.float32 else torch.float64), torch.device("cpu")
+
+    def stream(self):
+        import contextlib
+        return contextlib.nullcontext()
+
+    def vector(self, x64):
+        return x64.detach().cpu().numpy().astype(self.A.dtype)
+
+    def as64(self, x):
+        import numpy as np
+        import torch
+        return torch.from_numpy(np.array(x.detach().cpu() if hasattr(x, "detach") else x, dtype=np.float64).reshape(-1))
+
+    def dots(self, x):
+        return self.A @ x
+
+    def loss(self, dots, s=1.0):
+        from .host_route import host_margin_stats
+        st = host_margin_stats("logistic", dots, self.y, s)
+        return st[0] / self.N, st[1]
+
+    def gradient(self, x):
+        import numpy as np
+        import torch
+        t = (self.y * (self.A @ x)).astype(np.float64)
+        e = np.exp(-np.abs(t))
+        p = np.where(t >= 0, e / (1.0 + e), 1.0 / (1.0 + e))           # sigma(-t)
+        c = (-(self.y.astype(np.float64)) * p / self.N).astype(self.A.dtype)
+        return torch.from_numpy((self.A.T @ c).astype(np.float64))
+
+    def hessian(self, dots):
+        import numpy as np
+        import torch
+        from .host_route import host_gram
+        t = self.y.astype(np.float64) * np.asarray(dots, np.float64)
+        w = _sigmoid_weights(torch.from_numpy(t)).numpy()
+        return torch.from_numpy(host_gram(self.A, self.y, w)[0])
+
+    def certificate(self, x, mu, gamma):
+        return _certificate(self, self.as64(x), self.gradient(x), self.dots(x), mu, gamma)
+
+
+def _certificate(rows, x64, grad, dots, mu, gamma):
+    """The certificate of section 8.7 at x from its gradient (float64 d-vector) and its row dots: one margin_stats reduction at
+    s = min(1, mu / ||grad||_inf), no pass over A."""
+    import torch
+    ginf = float(grad.abs().max())
+    s = 1.0 if ginf == 0 else min(1.0, mu / ginf)
+    F, entropy = rows.loss(dots, s)
+    v = x64 - gamma * grad
+    res = x64 - torch.sign(v) * torch.clamp(v.abs() - gamma * mu, min=0.0)
+    return assemble(F, mu * float(x64.abs().sum()), float(res.norm()) / gamma, ginf, float(x64 @ grad), 0.0, mu=mu,
+                    entropy=entropy, n=rows.N)
+
+
+def _model_stats(rows, G, u, device):
+    """GramStats of the quadratic model (1/2N)(z'G z - 2 u'z + c) as a least-squares problem: c = u'G^+ u, the smallest constant for
+    which [[G, u], [u', c]] is positive semidefinite, so that lasso_path's duality gap is a gap of this model (u lies in the range of G up
+    to the samples whose weight underflowed; components of u along eigenvalues below 2^-40 lambda_max are left out of c)."""
+    import torch
+    G, u = G.to(device), u.to(device)
+    lam, Q = torch.linalg.eigh(G)
+    keep = lam > lam[-1] * 2.0 ** -40
+    c = float((((Q.T @ u)[keep]) ** 2 / lam[keep]).sum()) if bool(keep.any()) else 0.0
+    return GramStats(rows.N, rows.d, G, u, torch.zeros_like(u), 0.0, c, 1.0, "ls", torch.float64)
+
+
+def logistic_mu_max(rows) -> float:
+    """||grad f(0)||_inf = ||A'y||_inf / (2 N): the smallest l1 weight at which x = 0 minimises Phi.  One full-gradient pass."""
+    import torch
+    with rows.stream():
+        return float(rows.gradient(rows.vector(torch.zeros(rows.d, dtype=torch.float64))).abs().max())
+
+
+def logistic_newton(rows, mu, x0=None, gap=1e-9, max_outer=30, gamma=1.0, subproblem_device=None) -> NewtonResult:
+    """Minimise (1/N) sum_i log(1 + exp(-y_i a_i'x)) + mu ||x||_1 over rows (DeviceRows or HostRows) by the proximal Newton
+    iteration of this module's header -> NewtonResult.  mu > 0; x0: None (zeros) or a d-vector; gap: the relative duality gap asked
+    for; gamma: the step of the certificate's prox residual (reported only); subproblem_device: where the d x d lasso is solved
+    (None: the host up to d = 2048, the rows' device beyond)."""
+    import torch
+    mu = float(mu)
+    if not (mu > 0 and math.isfinite(mu)):
+        raise ValueError("logistic_newton needs an l1 weight mu > 0 and finite")
+    if not (gap > 0 and max_outer >= 0):
+        raise ValueError("gap must be > 0 and max_outer >= 0")
+    sub = torch.device(subproblem_device) if subproblem_device is not None else (torch.device("cpu") if rows.d <= HOST_SUBPROBLEM_D else rows.device)
+    # every torch operation of the iteration -- the vectors between the library's calls, G x, the line search's trial points -- runs on
+    # the rows' stream (DeviceRows.stream): in order with the kernels on either side of it, whatever torch's current stream is
+    with rows.stream():
+        x = rows.vector(torch.zeros(rows.d, dtype=torch.float64) if x0 is None else rows.as64(x0))
+        eps = float(torch.finfo(rows.dtype).eps)
+        n_gram = n_first = outer = 0
+        last = None
+        dots = rows.dots(x)
+        n_first += 1
+        reason = "max_outer"
+        while True:
+            x64 = rows.as64(x)
+            grad = rows.gradient(x)
+            n_first += 1
+            cert = _certificate(rows, x64, grad, dots, mu, gamma)
+            if cert.gap <= gap * max(1.0, cert.objective):
+                reason = "gap"
+                break
+            if last is not None and last.objective - cert.objective <= RESOLUTION * eps * max(1.0, abs(last.objective)) and not cert.gap <= 0.5 * last.gap:
+                reason = "stalled"
+                break
+            last = cert
+            if outer >= max_outer:
+                break
+            G = rows.hessian(dots)
+            n_gram += 1
+            outer += 1
+            u = G @ x64 - rows.N * grad
+            model = _model_stats(rows, G, u, sub)
+            xhat = lasso_path(model, [mu], x0=x64.to(sub), gap=INNER_FACTOR * gap, dtype=torch.float64).x[0].to(x64.device)
+            delta = xhat - x64
+            decrease = float(grad @ delta) + mu * (float(xhat.abs().sum()) - float(x64.abs().sum()))
+            accepted = False
+            if decrease < 0:
+                s = 1.0
+                for _ in range(MAX_HALVINGS):
+                    xt = rows.vector(x64 + s * delta)
+                    dt = rows.dots(xt)
+                    n_first += 1
+                    phi = rows.loss(dt)[0] + mu * float(rows.as64(xt).abs().sum())
+                    if phi <= cert.objective + ARMIJO * s * decrease:
+                        x, dots, accepted = xt, dt, True
+                        break
+                    s *= 0.5
+            if not accepted:
+                reason = "stalled"
+                break
+        final = rows.certificate(x, mu, gamma)
+        n_first += 1
+        converged = bool(final.gap <= gap * max(1.0, final.objective))
+        if reason == "gap" and not converged:
+            # the iteration's own evaluation of the gap (full gradient + margin statistics) met the bound and the certificate's pass over the
+            # same vector does not: two orders of addition differ by more than the gap asked for -- it lies below the noise of the rows' type
+            reason = "stalled"
+    return NewtonResult(x, final, outer, Passes(n_gram, n_first), converged, reason)
+
+
+def logistic_path(rows, mus, x0=None, gap=1e-9, max_outer=30, gamma=1.0, subproblem_device=None) -> list:
+    """logistic_newton for every l1 weight of `mus`, in the given order, each solve warm-started from the one before (the first from
+    x0) -> a list of NewtonResult.  A decreasing sequence from logistic_mu_max(rows) down is the regularisation path."""
+    out = []
+    for mu in mus:
+        r = logistic_newton(rows, mu, x0=x0, gap=gap, max_outer=max_outer, gamma=gamma, subproblem_device=subproblem_device)
+        out.append(r)
+        x0 = r.x
+    return out

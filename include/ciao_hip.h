@@ -317,6 +317,25 @@ CIAO_API int32_t ciao_scale_columns(ciao_ctx *ctx, const ciao_problem *p, const 
  * ciao_col_moments (the ranks' matrices are not combined).  Workspace: at most 256 MiB of partial tiles.  Does not synchronise, except
  * where that workspace has to grow. */
 CIAO_API int32_t ciao_gram(ciao_ctx *ctx, const ciao_problem *p, double *G, int64_t ldg, double *u, double *colsum, double *bsum);
+/* EXTENSION beyond the reference: ciao_gram with a weight per row -- A' diag(w) A and the weighted sums, in the same one pass on the
+ * matrix cores.  DESIGN.md section 8.13.  w: a device vector of N DOUBLES (the local rows') at any 8-byte-aligned address; nothing beyond
+ * w[N-1] is read.  Over the N resident rows, for i, j < d:
+ *     G[i * ldg + j] = sum_n w_n A[n,i] A[n,j]     u[j] = sum_n w_n A[n,j] b_n      colsum[j] = sum_n w_n A[n,j]
+ *     bsum[0] = sum_n w_n b_n                      bsum[1] = sum_n w_n b_n^2        bsum[2] = sum_n w_n
+ * bsum: 3 device DOUBLES here; G, ldg, u, colsum and the NULL rule as ciao_gram (u, colsum, bsum may each be NULL and the others' bits do
+ * not depend on it).  WHERE THE WEIGHT ENTERS: exactly one operand of every product is w_n times an element -- w_n A[n,j] for G[i][j] with
+ * i <= j (the other triangle is its mirror: both hold the same bits), w_n b_n for u and bsum[0..1], w_n for colsum and bsum[2] -- formed
+ * in double with ONE rounding; the other operand is the raw element, and no square root of w is taken.  So any finite weight is allowed,
+ * negative ones included; integer weights on integer rows stay exact; w = 1 gives ciao_gram's bits (1 a is exact, the order of addition
+ * is the same); 0/1 weights give the statistics of a row subset without copying rows.  A weight of zero does NOT mask a non-finite
+ * element: 0 inf = NaN.  Plan, tiles, workspace and the order of addition are ciao_gram's: a function of (N, d) alone, not of ld, of
+ * the bases of A or w, of p->dtype, of the NULL outputs or of the values of w; bitwise reproducible.  Refused with CIAO_ERR_ARG and
+ * nothing launched: a NULL or misaligned w, and everything ciao_gram refuses (complex problems, CIAO_LOSS_ZERO, d > 4096, ldg < d,
+ * NULL ctx / p / G).  N = 0: every output is set to zero, no kernel is launched (w may then be NULL).  On a row-sharded context: the
+ * LOCAL rows only.
+ * Workspace: ciao_gram's.  Does not synchronise, except where that workspace has to grow. */
+CIAO_API int32_t ciao_gram_weighted(ciao_ctx *ctx, const ciao_problem *p, const double *w, double *G, int64_t ldg, double *u, double *colsum,
+                                    double *bsum);
 
 /* ---- SVRG / SVRG++  (SVRG/SVRG_basic.jl) -------------------------------------------------------------------- */
 /* Base.iterate(iter), :57-66: av = full gradient at x0; z_full = x0; z = 0; w = x0. */
