@@ -10,7 +10,7 @@ The directory name contains a dot, so it is loaded under the importable alias `c
     sampling.py      injected index streams (the reference's RNG draws are an explicit input here)
     solvers.py       SVRG / SAGA / SAG / Finito constructors, functors, iterator(), solution()
     parallel.py      row sharding + torch.distributed (RCCL) all-reduce hook
-    gram.py          Gram statistics (plain and with a weight per row) and what follows from them in d-space: GramLasso, lasso_path
+    gram.py          Gram statistics (plain and with a weight per row) and what follows from them in d-space: GramLasso, lasso_path, lasso_cd (coordinate descent: ciao_gram_cd)
     newton.py        a proximal Newton path for l1-logistic rows on the weighted Gram pass (DeviceRows / HostRows)
     julia/           the Julia wrapper module (written against the same ABI; cannot run in this image)
 Importing this package does not need a GPU; creating a Context does.  There is no CPU fallback.
@@ -19,6 +19,8 @@ from . import _lib
 from .sampling import FixedStream, IndexStream
 
 __all__ = ["_lib", "IndexStream", "FixedStream"]
+# the coordinate-descent route of the d-space lasso, by name from the package
+_ELSEWHERE = {"lasso_cd": "gram", "host_gram_cd": "host_route"}
 
 
 def __getattr__(name):
@@ -30,4 +32,6 @@ def __getattr__(name):
             return getattr(m, name)
         if name == mod:
             return m
+    if name in _ELSEWHERE:
+        return getattr(importlib.import_module(f"{__name__}.{_ELSEWHERE[name]}"), name)
     raise AttributeError(name)

@@ -1827,6 +1827,24 @@ int32_t ciao_gram_weighted(ciao_ctx *ctx, const ciao_problem *p, const double *w
                                 : launch_gram_weighted<float>(ctx, p, w, G, ldg, u, colsum, bsum);
 }
 
+int32_t ciao_gram_cd(ciao_ctx *ctx, int64_t d, int64_t K, const double *G, int64_t ldg, const double *u, const double *inv, const double *tau,
+                     double *X, int64_t ldx, double tol, int32_t max_sweeps, double *R, int64_t ldr, double *stat)
+{
+    CIAO_REQUIRE(ctx && G && u && inv && tau && X && stat, "ciao_gram_cd: the context, G, u, inv, tau, X or stat is NULL");
+    CIAO_ENTER(ctx);
+    CIAO_REQUIRE(d >= 1 && d <= 4096, "ciao_gram_cd takes 1 <= d <= 4096 coordinates (got d=%lld: x, r and the diagonal live in LDS)", (long long)d);
+    CIAO_REQUIRE(K >= 1 && K <= 4096, "ciao_gram_cd takes 1 <= K <= 4096 models in one launch (got K=%lld)", (long long)K);
+    CIAO_REQUIRE(ldg >= d, "ciao_gram_cd: the row stride of G, ldg=%lld, is below d=%lld", (long long)ldg, (long long)d);
+    CIAO_REQUIRE(ldx >= d, "ciao_gram_cd: the stride of X, ldx=%lld, is below d=%lld", (long long)ldx, (long long)d);
+    CIAO_REQUIRE(!R || ldr >= d, "ciao_gram_cd: the stride of R, ldr=%lld, is below d=%lld", (long long)ldr, (long long)d);
+    CIAO_REQUIRE(((reinterpret_cast<uintptr_t>(G) | reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(inv) | reinterpret_cast<uintptr_t>(tau) |
+                   reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(R) | reinterpret_cast<uintptr_t>(stat)) & 7u) == 0,
+                 "ciao_gram_cd: a buffer is not aligned to 8 bytes");
+    CIAO_REQUIRE(tol >= 0.0, "ciao_gram_cd: tol must be >= 0 (got %g)", tol);
+    CIAO_REQUIRE(max_sweeps >= 1 && max_sweeps <= 1024, "ciao_gram_cd takes 1 <= max_sweeps <= 1024 per launch (got %d): relaunch from the returned X", (int)max_sweeps);
+    return launch_gram_cd(ctx, d, K, G, ldg, u, inv, tau, X, ldx, tol, max_sweeps, R, ldr, stat);
+}
+
 int32_t ciao_screen(ciao_ctx *ctx, int32_t dtype, int64_t d, const void *grad, const double *colsq, double s, double kappa, double mu,
                     uint8_t *keep, int64_t *n_kept_host)
 {

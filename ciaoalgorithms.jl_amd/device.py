@@ -651,6 +651,49 @@ class Context:
             L.check(self.lib.ciao_gram_weighted(self._h, F.ref, _ptr(weights), _ptr(G), ldg, *outp))
         return (G, *outs)
 
+    def gram_cd(self, G, u, inv, tau, X, tol, max_sweeps, R=True, stat=None):
+        """(X, R, stat): cyclic coordinate descent with covariance updates on a Gram matrix, K models in one launch (include/ciao_hip.h:
+        ciao_gram_cd; DESIGN.md section 8.14, with the method to the bit and its numpy mirror).  All float64 device tensors: G (d, d)
+        row-major with any row stride >= d; u, inv d-vectors (inv_j = 1 / G_jj where G_jj > 0, else 0); tau a K-vector (mu_k N / lam);
+        X (K, d) with any row stride >= d: the warm starts, OVERWRITTEN with the results.  R: a (K, d) matrix to receive the final
+        r = u - G x, True for a fresh one, None / False to leave it out; stat: a contiguous (K, 4) matrix, fresh by default: sweeps,
+        non-zero updates, largest change of the last full sweep, state (1 converged, 0 sweep budget spent, 2 not finite).
+        0 <= tol; 1 <= max_sweeps <= 1024; d, K <= 4096.  Does not synchronise."""
+        dev = f"cuda:{self.device}"
+
+        def fresh(*shape):
+            t = torch.empty(shape, dtype=torch.float64, device=dev)
+            if self.stream is not None:
+                t.record_stream(self.stream)
+            return t
+
+        def mat(t, name, rows, cols):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == self.device and t.dtype == torch.float64 and t.dim() == 2
+                    and tuple(t.shape) == (rows, cols) and (t.stride(1) == 1 or cols == 1) and (rows == 1 or t.stride(0) >= cols)):
+                raise ValueError(f"{name}: need a row-major float64 matrix of shape ({rows}, {cols}) on {dev}")
+            return int(t.stride(0)) if rows > 1 else cols
+
+        if not (isinstance(X, torch.Tensor) and X.dim() == 2):
+            raise ValueError("X: need a (K, d) float64 device matrix")
+        K, d = int(X.shape[0]), int(X.shape[1])
+        ldx = mat(X, "X", K, d)
+        ldg = mat(G, "G", d, d)
+        self._dvec(u, "u", d)
+        self._dvec(inv, "inv", d)
+        self._dvec(tau, "tau", K)
+        if R is True:
+            R = fresh(K, d)
+        elif R is None or R is False:
+            R = None
+        ldr = mat(R, "R", K, d) if R is not None else 0
+        if stat is None:
+            stat = fresh(K, 4)
+        elif not (isinstance(stat, torch.Tensor) and stat.is_cuda and stat.dtype == torch.float64 and tuple(stat.shape) == (K, 4) and stat.is_contiguous()):
+            raise ValueError(f"stat: need a contiguous float64 device matrix of shape ({K}, 4)")
+        L.check(self.lib.ciao_gram_cd(self._h, d, K, _ptr(G), ldg, _ptr(u), _ptr(inv), _ptr(tau), _ptr(X), ldx, float(tol), int(max_sweeps),
+                                      _ptr(R), ldr, _ptr(stat)))
+        return X, R, stat
+
     # -- SVRG ------------------------------------------------------------------------------------------------------------
     def svrg_init(self, p, x0, av, z, z_full, w):
         L.check(self.lib.ciao_svrg_init(self._h, p.ref, self._vec(x0, p, "x0"), self._vec(av, p, "av"), self._vec(z, p, "z"),

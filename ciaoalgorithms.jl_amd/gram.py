@@ -225,19 +225,41 @@ class GramLasso:
 class LassoPath(NamedTuple):
     x: list               # K d-vectors in the rows' dtype, on G's device
     certificates: list    # K CertificateResult, taken AT those (rounded) vectors
-    iterations: int       # FISTA iterations made
+    iterations: int       # FISTA iterations made (lasso_path) / sweeps made, over all models (lasso_cd)
     converged: list       # K booleans: the model met its gap before maxit
 
 
-def lasso_path(stats: GramStats, mus, x0=None, gap=1e-9, maxit=20000, check_every=10, dtype=None) -> LassoPath:
+def _path_gaps(q, mu, X):
+    """(gap_k, objective_k) of the K columns of X (d x K, float64) for the l1 weights mu (a K-vector on X's device): the certified duality
+    gap of certificate.assemble's lasso formula, all K at once.  lasso_path and lasso_cd stop on it."""
+    import torch
+    s = q.stats
+    c = s.lam / s.N
+    grad = c * (s.G @ X - s.u[:, None])
+    Fv = q.value(X)
+    gv = mu * X.abs().sum(0)
+    ginf = grad.abs().amax(0)
+    sc = torch.where(ginf > 0, torch.clamp(mu / ginf, max=1.0), torch.ones_like(ginf))
+    dual = Fv * (2 * sc - sc * sc) - sc * (X * grad).sum(0)
+    return Fv + gv - dual, Fv + gv
+
+
+def lasso_path(stats: GramStats, mus, x0=None, gap=1e-9, maxit=20000, check_every=10, dtype=None, method="fista", ctx=None) -> LassoPath:
     """The lasso min_x f(x) + mu_k ||x||_1 for every mu_k of `mus`, in d-space: FISTA with the step 1 / smoothness_exact(stats), all K
     models as one d x K matrix (one d x d x K product per iteration; A is never read).  Model k stops -- its column is frozen -- at the
     first check (every `check_every` iterations) with gap_k <= gap * max(1, objective_k), the gap being the certified duality gap of
     certificate.assemble.  x0: None (zeros), a d-vector for all, or K of them.  Returns LassoPath: the K iterates in the rows' dtype
     (stats.dtype; dtype= overrides), ready for solve_together and score_many, with the certificates of exactly those vectors (rounding
     an iterate to float32 moves its gap: the certificate says what was reached, `converged` what the float64 iteration met).
-    LeastSquares statistics only."""
+    LeastSquares statistics only.
+
+    method: "fista" (the default: the iteration above) or "cd": lasso_cd(stats, mus, x0, gap, ctx=ctx, dtype=dtype) -- coordinate descent,
+    on the device kernel where stats.G is on the GPU and a Context is given (maxit and check_every belong to FISTA and are not used)."""
     import torch
+    if method == "cd":
+        return lasso_cd(stats, mus, x0=x0, gap=gap, ctx=ctx, dtype=dtype)
+    if method != "fista":
+        raise ValueError(f"method must be 'fista' or 'cd' (got {method!r})")
     q = GramLasso(stats)
     s = stats
     mus = [float(m) for m in mus]
@@ -264,13 +286,7 @@ def lasso_path(stats: GramStats, mus, x0=None, gap=1e-9, maxit=20000, check_ever
     it = 0
 
     def gaps(X):
-        grad = c * (s.G @ X - s.u[:, None])
-        Fv = q.value(X)
-        gv = mu * X.abs().sum(0)
-        ginf = grad.abs().amax(0)
-        sc = torch.where(ginf > 0, torch.clamp(mu / ginf, max=1.0), torch.ones_like(ginf))
-        dual = Fv * (2 * sc - sc * sc) - sc * (X * grad).sum(0)
-        return Fv + gv - dual, Fv + gv
+        return _path_gaps(q, mu, X)
 
     while it < maxit:
         grad = c * (s.G @ Y - s.u[:, None])
@@ -290,3 +306,98 @@ def lasso_path(stats: GramStats, mus, x0=None, gap=1e-9, maxit=20000, check_ever
     xs = [X[:, k].to(out_dtype).contiguous() for k in range(K)]
     done = (~active).tolist()
     return LassoPath(xs, [q.certificate(x, m, step) for x, m in zip(xs, mus)], it, done)
+
+
+CD_FIRST_TOL = 1e-7       # lasso_cd's first sweep tolerance, times sum b^2 (the change G_jj delta^2 has the units of x'G x)
+CD_TOL_DROP = 100.0       # ... divided by this for every model that has not met its gap
+CD_MAX_LAUNCH = 1024      # sweeps one launch may make (ciao_gram_cd's bound)
+
+
+def lasso_cd(stats: GramStats, mus, x0=None, gap=1e-9, max_sweeps=2000, ctx=None, dtype=None) -> LassoPath:
+    """lasso_path's problem by cyclic coordinate descent with covariance updates: an update reads one row of G, a
+    coordinate that stays at zero reads none.  With stats.G on the GPU and a device.Context `ctx` the sweeps run in ONE kernel launch for
+    all models (Context.gram_cd: a workgroup per model); otherwise in numpy (host_route.host_gram_cd).  The two give the same bits.
+
+    The driver: launch with the sweep tolerance tol = 1e-7 sum b^2 on the largest change G_jj delta^2 of a sweep; take the certified
+    duality gaps of all K models (lasso_path's formula); freeze the models with gap_k <= gap max(1, objective_k); relaunch the rest,
+    warm, with tol / 100; until all have met the gap or a model has made max_sweeps sweeps.  A model whose launch moved no coordinate
+    at all is at a fixed point of the update in floating point and is frozen as it is (converged = False unless its gap is met).
+    x0, dtype and the returned LassoPath are lasso_path's; iterations = the sweeps made, summed over the models.  LeastSquares
+    statistics only, weighted ones included."""
+    import numpy as np
+    import torch
+    q = GramLasso(stats)
+    s = stats
+    mus = [float(m) for m in mus]
+    K = len(mus)
+    if K < 1 or any(not (m > 0 and math.isfinite(m)) for m in mus):
+        raise ValueError("lasso_cd needs at least one l1 weight, every one > 0 and finite")
+    if not (gap > 0 and max_sweeps >= 1):
+        raise ValueError("gap must be > 0 and max_sweeps >= 1")
+    dev = s.G.device
+    on_device = dev.type == "cuda" and ctx is not None
+    if dev.type == "cuda" and ctx is None:
+        raise L.CiaoError(L.ERR_ARG, "lasso_cd on device statistics needs the Context to launch on (ctx=); stats.to('cpu') runs the numpy twin")
+    if on_device:
+        from .stepsize import _on_stream
+        stream = lambda: _on_stream(ctx)   # noqa: E731
+    else:
+        import contextlib
+        stream = contextlib.nullcontext
+    with stream():
+        mu = torch.tensor(mus, dtype=torch.float64, device=dev)
+        if x0 is None:
+            X = torch.zeros((K, s.d), dtype=torch.float64, device=dev)
+        elif isinstance(x0, (list, tuple)):
+            if len(x0) != K:
+                raise ValueError(f"{len(x0)} starting points for {K} models")
+            X = torch.stack([q._x(v) for v in x0], dim=0).contiguous()
+        else:
+            X = q._x(x0)[None, :].repeat(K, 1)
+        c = s.lam / s.N
+        tau = torch.tensor([m / c for m in mus], dtype=torch.float64, device=dev)
+        diag = torch.diagonal(s.G)
+        inv = torch.where(diag > 0, 1.0 / diag, torch.zeros_like(diag)).contiguous()
+        G = s.G if s.G.stride(1) == 1 or s.d == 1 else s.G.contiguous()
+        u = s.u.contiguous()
+        tol = CD_FIRST_TOL * float(s.sum_bb)
+        if not (tol >= 0 and math.isfinite(tol)):
+            raise ValueError("sum_bb must be finite and >= 0")
+        used = [0] * K
+        done = [False] * K
+        live = list(range(K))
+        while live:
+            budget = min(CD_MAX_LAUNCH, max_sweeps - max(used[k] for k in live))
+            if budget < 1:
+                break
+            idx = torch.tensor(live, dtype=torch.long, device=dev)
+            Xl = X.index_select(0, idx).contiguous()
+            if on_device:
+                _, _, st = ctx.gram_cd(G, u, inv, tau.index_select(0, idx).contiguous(), Xl, tol, budget, R=None)
+                st = st.cpu().numpy()
+            else:
+                Xn, _, st = _host_cd(G, u, inv, tau.index_select(0, idx), Xl, tol, budget)
+                Xl = torch.from_numpy(Xn)
+            X.index_copy_(0, idx, Xl)
+            gp, obj = _path_gaps(q, mu.index_select(0, idx), Xl.t())
+            met = (gp <= gap * torch.clamp(obj, min=1.0)).tolist()
+            nxt = []
+            for pos, k in enumerate(live):
+                used[k] += int(st[pos, 0])
+                if met[pos]:
+                    done[k] = True
+                elif st[pos, 3] != 2 and st[pos, 1] > 0:
+                    nxt.append(k)
+            live = nxt
+            tol /= CD_TOL_DROP
+        out_dtype = dtype or s.dtype or torch.float64
+        xs = [X[k].to(out_dtype).contiguous() for k in range(K)]
+        gamma = 1.0 / float(diag.max()) / c if float(diag.max()) > 0 else 1.0
+        certs = [q.certificate(x, m, gamma) for x, m in zip(xs, mus)]
+    return LassoPath(xs, certs, int(np.sum(used)), done)
+
+
+def _host_cd(G, u, inv, tau, X, tol, max_sweeps):
+    """host_route.host_gram_cd on CPU torch tensors (G may have any strides)."""
+    from .host_route import host_gram_cd
+    return host_gram_cd(G.numpy(), u.numpy(), inv.numpy(), tau.numpy(), X.numpy(), tol, max_sweeps)

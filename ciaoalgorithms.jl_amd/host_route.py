@@ -490,6 +490,75 @@ def host_gram(A, b, weights=None):
     return G, A.T @ wb, A.T @ w, np.array([np.sum(wb), b @ wb, np.sum(w)])
 
 
+def host_gram_cd(G, u, inv, tau, X, tol, max_sweeps):
+    """ciao_gram_cd in numpy (float64) -> (X, R, stat): cyclic coordinate descent with covariance updates on a Gram matrix, the
+    SPECIFICATION of the device kernel (csrc/gramcd_kernels.h) and its CPU twin -- the two agree bit for bit.
+    G: d x d (only row j is read for coordinate j); u, inv: d (inv_j = 1 / G_jj where G_jj > 0, else 0); tau: K; X: K x d warm starts
+    (not modified; the results are returned); tol >= 0; 1 <= max_sweeps.  R: the final r = u - G x as accumulated; stat: K x 4 =
+    {sweeps, non-zero updates, largest change of the last completed full sweep, state (1 converged, 0 budget spent, 2 not finite)}.
+    Row-vector operations only, so every product is rounded before it is added, as in the kernel."""
+    G, u, inv = np.asarray(G, np.float64), np.asarray(u, np.float64), np.asarray(inv, np.float64)
+    tau = np.asarray(tau, np.float64).reshape(-1)
+    X = np.array(X, dtype=np.float64, ndmin=2)
+    K, d = X.shape
+    if G.shape != (d, d) or u.shape != (d,) or inv.shape != (d,) or tau.shape != (K,):
+        raise ValueError("host_gram_cd: G must be d x d, u and inv d-vectors, tau a K-vector and X K x d")
+    if not (tol >= 0) or max_sweeps < 1:
+        raise ValueError("host_gram_cd: tol must be >= 0 and max_sweeps >= 1")
+    R = np.empty((K, d))
+    stat = np.zeros((K, 4))
+    diag = np.diagonal(G).copy()
+    with np.errstate(all="ignore"):
+        for k in range(K):
+            x, t = X[k], tau[k]
+            r = u.copy()
+            for j in np.flatnonzero(x != 0):
+                r -= x[j] * G[j]
+            sweeps, nupd, last_full, state, active = 0, 0, 0.0, 0, False
+            while True:
+                if sweeps >= max_sweeps:
+                    state = 0
+                    break
+                sweeps += 1
+                big, support, bad = 0.0, False, False
+                for j in range(d):
+                    xj = x[j]
+                    if active and xj == 0:
+                        continue
+                    rho = r[j] + diag[j] * xj
+                    a = abs(rho) - t
+                    if a <= 0 and xj == 0:
+                        continue                      # x+ = 0 = x_j: nothing moves
+                    xp = 0.0 if a <= 0 else np.copysign(a, rho) * inv[j]
+                    delta = xp - xj
+                    if not np.isfinite(delta):
+                        bad = True
+                        break
+                    if delta != 0:
+                        r -= delta * G[j]
+                        x[j] = xp
+                        nupd += 1
+                        ch = diag[j] * (delta * delta)
+                        if ch > big:
+                            big = ch
+                        if (xj == 0) != (xp == 0):
+                            support = True
+                if bad:
+                    state = 2
+                    break
+                if not active:
+                    last_full = big
+                    if big <= tol and not support:
+                        state = 1
+                        break
+                    active = True
+                elif big <= tol:
+                    active = False
+            R[k] = r
+            stat[k] = (sweeps, nupd, last_full, state)
+    return X, R, stat
+
+
 def host_standardize(A, b=None, center=True, scale=True, refine=True):
     """standardize.standardize in numpy on a host matrix -> (A_std, b_std, mean, scale, b_mean).  The moments are
     standardize.host_column_moments' (the same shift, the same refinement rule, the same default: always refined); scale_j = 1 / sqrt(var_j) with the population variance, 1

@@ -549,6 +549,23 @@ function gram_stats(F::PackedF{R}) where {R}
             kind = ls ? :ls : :logistic)
 end
 
+# gram_cd: cyclic coordinate descent with covariance updates for the lasso on a Gram matrix, K models in one launch (ciao_gram_cd; Python
+# twins: device.Context.gram_cd, gram.lasso_cd; DESIGN.md section 8.14).  G: d x d Float64 (symmetric, so its layout does not matter),
+# u, inv: d (inv[j] = 1 / G[j,j] where that is > 0, else 0), tau: K (mu_k N / lam), X: d x K, the warm starts, overwritten with the results.
+# Returns (X, R, stat): R = u - G x per model (d x K), stat 4 x K = sweeps, non-zero updates, largest change of the last full sweep,
+# state (1 converged, 0 sweep budget spent, 2 not finite).  Does not synchronise.
+function gram_cd(G::ROCArray{Float64}, u::ROCArray{Float64}, inv::ROCArray{Float64}, tau::ROCArray{Float64}, X::ROCArray{Float64};
+                 tol::Float64 = 0.0, max_sweeps::Int = 1024)
+    d, K = size(X, 1), size(X, 2)
+    (size(G) == (d, d) && length(u) == d && length(inv) == d && length(tau) == K) || throw(ArgumentError("gram_cd: G must be d x d, u and inv of length d, tau of length K"))
+    R = ROCArray{Float64}(undef, d, K)
+    stat = ROCArray{Float64}(undef, 4, K)
+    check(ccall((:ciao_gram_cd, libciao), Int32,
+                (Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float64, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}),
+                context().h, Int64(d), Int64(K), dptr(G), Int64(d), dptr(u), dptr(inv), dptr(tau), dptr(X), Int64(d), tol, Int32(max_sweeps), dptr(R), Int64(d), dptr(stat)))
+    return X, R, stat
+end
+
 # ======================================================================================================================
 # SVRG  (src/algorithms/SVRG/SVRG.jl, SVRG_basic.jl)
 # ======================================================================================================================

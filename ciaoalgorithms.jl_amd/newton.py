@@ -32,7 +32,7 @@ from typing import NamedTuple
 
 from . import _lib as L
 from .certificate import CertificateResult, assemble
-from .gram import GramStats, lasso_path
+from .gram import GramStats, lasso_cd, lasso_path
 
 INNER_FACTOR = 0.1        # the subproblem is solved to INNER_FACTOR * gap (relative to max(1, model value), as lasso_path measures it)
 ARMIJO = 1e-4
@@ -210,15 +210,21 @@ def logistic_mu_max(rows) -> float:
         return float(rows.gradient(rows.vector(torch.zeros(rows.d, dtype=torch.float64))).abs().max())
 
 
-def logistic_newton(rows, mu, x0=None, gap=1e-9, max_outer=30, gamma=1.0, subproblem_device=None) -> NewtonResult:
+def logistic_newton(rows, mu, x0=None, gap=1e-9, max_outer=30, gamma=1.0, subproblem_device=None, subproblem="fista") -> NewtonResult:
     """Minimise (1/N) sum_i log(1 + exp(-y_i a_i'x)) + mu ||x||_1 over rows (DeviceRows or HostRows) by the proximal Newton
     iteration of this module's header -> NewtonResult.  mu > 0; x0: None (zeros) or a d-vector; gap: the relative duality gap asked
     for; gamma: the step of the certificate's prox residual (reported only); subproblem_device: where the d x d lasso is solved
-    (None: the host up to d = 2048, the rows' device beyond)."""
+    (None: the host up to d = 2048, the rows' device beyond).
+
+    subproblem: "fista" (the default: gram.lasso_path) or "cd": gram.lasso_cd, coordinate descent on the model's Gram matrix (DESIGN.md
+    section 8.14) -- on the device kernel, where G already lies, when the rows are DeviceRows (subproblem_device is then not used), and
+    in numpy for HostRows."""
     import torch
     mu = float(mu)
     if not (mu > 0 and math.isfinite(mu)):
         raise ValueError("logistic_newton needs an l1 weight mu > 0 and finite")
+    if subproblem not in ("fista", "cd"):
+        raise ValueError(f"subproblem must be 'fista' or 'cd' (got {subproblem!r})")
     if not (gap > 0 and max_outer >= 0):
         raise ValueError("gap must be > 0 and max_outer >= 0")
     sub = torch.device(subproblem_device) if subproblem_device is not None else (torch.device("cpu") if rows.d <= HOST_SUBPROBLEM_D else rows.device)
@@ -250,8 +256,12 @@ def logistic_newton(rows, mu, x0=None, gap=1e-9, max_outer=30, gamma=1.0, subpro
             n_gram += 1
             outer += 1
             u = G @ x64 - rows.N * grad
-            model = _model_stats(rows, G, u, sub)
-            xhat = lasso_path(model, [mu], x0=x64.to(sub), gap=INNER_FACTOR * gap, dtype=torch.float64).x[0].to(x64.device)
+            if subproblem == "cd":
+                model = _model_stats(rows, G, u, G.device)
+                xhat = lasso_cd(model, [mu], x0=x64, gap=INNER_FACTOR * gap, ctx=getattr(rows, "ctx", None), dtype=torch.float64).x[0]
+            else:
+                model = _model_stats(rows, G, u, sub)
+                xhat = lasso_path(model, [mu], x0=x64.to(sub), gap=INNER_FACTOR * gap, dtype=torch.float64).x[0].to(x64.device)
             delta = xhat - x64
             decrease = float(grad @ delta) + mu * (float(xhat.abs().sum()) - float(x64.abs().sum()))
             accepted = False
@@ -279,12 +289,12 @@ def logistic_newton(rows, mu, x0=None, gap=1e-9, max_outer=30, gamma=1.0, subpro
     return NewtonResult(x, final, outer, Passes(n_gram, n_first), converged, reason)
 
 
-def logistic_path(rows, mus, x0=None, gap=1e-9, max_outer=30, gamma=1.0, subproblem_device=None) -> list:
+def logistic_path(rows, mus, x0=None, gap=1e-9, max_outer=30, gamma=1.0, subproblem_device=None, subproblem="fista") -> list:
     """logistic_newton for every l1 weight of `mus`, in the given order, each solve warm-started from the one before (the first from
     x0) -> a list of NewtonResult.  A decreasing sequence from logistic_mu_max(rows) down is the regularisation path."""
     out = []
     for mu in mus:
-        r = logistic_newton(rows, mu, x0=x0, gap=gap, max_outer=max_outer, gamma=gamma, subproblem_device=subproblem_device)
+        r = logistic_newton(rows, mu, x0=x0, gap=gap, max_outer=max_outer, gamma=gamma, subproblem_device=subproblem_device, subproblem=subproblem)
         out.append(r)
         x0 = r.x
     return out

@@ -336,6 +336,27 @@ CIAO_API int32_t ciao_gram(ciao_ctx *ctx, const ciao_problem *p, double *G, int6
  * Workspace: ciao_gram's.  Does not synchronise, except where that workspace has to grow. */
 CIAO_API int32_t ciao_gram_weighted(ciao_ctx *ctx, const ciao_problem *p, const double *w, double *G, int64_t ldg, double *u, double *colsum,
                                     double *bsum);
+/* EXTENSION beyond the reference: cyclic coordinate descent with covariance updates for the lasso on a Gram matrix (glmnet's inner loop),
+ * K models in one launch, one workgroup each.  DESIGN.md section 8.14.  Everything is DOUBLE and on the device:
+ *     min_x (c/2)(x'G x - 2 u'x + const) + mu_k ||x||_1,   tau[k] = mu_k / c
+ * G: d x d at row stride ldg (symmetric: only ROW j is read for coordinate j, never a column beyond d-1); u: d; inv: d, inv[j] = 1 / G[j][j]
+ * where that is > 0 and 0 elsewhere (the kernel never divides); tau: K; X: K vectors of d at stride ldx, the warm starts on entry and the
+ * results on exit; R: K vectors of d at stride ldr, or NULL: the final r = u - G x as accumulated; stat: K x 4 doubles {sweeps made,
+ * non-zero updates made, largest change of the last completed full sweep, state}.
+ *     start      r = u; for j ascending with x_j != 0: r_i -= x_j G[j][i]
+ *     update(j)  rho = r_j + G_jj x_j; a = |rho| - tau; x+ = 0 if a <= 0, else copysign(a, rho) inv_j; delta = x+ - x_j; delta not finite:
+ *                the model ends at once, state 2, x_j unchanged; delta != 0: r_i -= delta G[j][i] for all i, then x_j = x+;
+ *                change = G_jj delta^2; the support changes if exactly one of x_j, x+ is 0
+ *     loop       a full sweep (j = 0 .. d-1); largest change <= tol and support unchanged: state 1 (converged).  Otherwise active sweeps
+ *                (only the j with x_j != 0 at their turn) until one has largest change <= tol, then a full sweep again.  Every sweep counts
+ *                against max_sweeps; the budget spent: state 0 (call again from the returned X).
+ * Every product is rounded before it is added and no sum over coordinates is formed: the results are a function of the inputs' bits alone,
+ * not of K, of a model's place among the K, of ldg / ldx / ldr, of the bases or of the run (host_route.host_gram_cd reproduces them in
+ * numpy).  Refused with CIAO_ERR_ARG and nothing launched: NULL ctx / G / u / inv / tau / X / stat; d < 1 or > 4096; K < 1 or > 4096;
+ * ldg < d, ldx < d, ldr < d with R given; a base not aligned to 8 bytes; tol < 0 or NaN; max_sweeps < 1 or > 1024 (this bounds one
+ * launch's time).  Does not synchronise. */
+CIAO_API int32_t ciao_gram_cd(ciao_ctx *ctx, int64_t d, int64_t K, const double *G, int64_t ldg, const double *u, const double *inv,
+                              const double *tau, double *X, int64_t ldx, double tol, int32_t max_sweeps, double *R, int64_t ldr, double *stat);
 
 /* ---- SVRG / SVRG++  (SVRG/SVRG_basic.jl) -------------------------------------------------------------------- */
 /* Base.iterate(iter), :57-66: av = full gradient at x0; z_full = x0; z = 0; w = x0. */
