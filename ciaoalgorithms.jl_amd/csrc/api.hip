@@ -1827,6 +1827,32 @@ int32_t ciao_gram_weighted(ciao_ctx *ctx, const ciao_problem *p, const double *w
                                 : launch_gram_weighted<float>(ctx, p, w, G, ldg, u, colsum, bsum);
 }
 
+int32_t ciao_gram_rows(ciao_ctx *ctx, const ciao_problem *p, const int64_t *idx, int64_t M, const double *w, double *G, int64_t ldg, double *u,
+                       double *colsum, double *bsum)
+{
+    CIAO_REQUIRE(ctx && p && G, "ciao_gram_rows: the context, the problem or the output matrix G is NULL");
+    CIAO_REQUIRE(M >= 0, "ciao_gram_rows: the length of the row list, M=%lld, is negative", (long long)M);
+    CIAO_REQUIRE(idx || M == 0, "ciao_gram_rows: the row list idx is NULL");
+    CIAO_ENTER(ctx);
+    CIAO_TRY(check_problem(ctx, p));
+    CIAO_REQUIRE(p->loss != CIAO_LOSS_LS_COMPLEX, "ciao_gram_rows covers real problems only (complex T: A'A of (re, im) pairs is not the Gram matrix of the complex rows)");
+    CIAO_REQUIRE(p->loss != CIAO_LOSS_ZERO, "ciao_gram_rows needs data rows (Zero() terms have no matrix A)");
+    CIAO_REQUIRE(ldg >= p->d, "ciao_gram_rows: the row stride of G, ldg=%lld, is below d=%lld", (long long)ldg, (long long)p->d);
+    CIAO_REQUIRE(p->d <= 4096, "ciao_gram_rows takes rows of at most 4096 elements (got d=%lld: G alone would be %.0f MiB)", (long long)p->d,
+                 (double)p->d * (double)p->d * 8.0 / 1048576.0);
+    CIAO_REQUIRE((reinterpret_cast<uintptr_t>(idx) & 7u) == 0, "ciao_gram_rows: the row list idx is not aligned to 8 bytes");
+    CIAO_REQUIRE((reinterpret_cast<uintptr_t>(w) & 7u) == 0, "ciao_gram_rows: the weight vector w is not aligned to 8 bytes");
+    if (M == 0 || p->N == 0) {   // an empty list (or no row that an entry could name): every sum is zero, nothing is launched
+        CIAO_HIP(hipMemset2DAsync(G, (size_t)ldg * sizeof(double), 0, (size_t)p->d * sizeof(double), (size_t)p->d, ctx->stream));
+        if (u) CIAO_HIP(hipMemsetAsync(u, 0, (size_t)p->d * sizeof(double), ctx->stream));
+        if (colsum) CIAO_HIP(hipMemsetAsync(colsum, 0, (size_t)p->d * sizeof(double), ctx->stream));
+        if (bsum) CIAO_HIP(hipMemsetAsync(bsum, 0, (w ? 3 : 2) * sizeof(double), ctx->stream));
+        return CIAO_OK;
+    }
+    return p->dtype == CIAO_F64 ? launch_gram_rows<double>(ctx, p, idx, M, w, G, ldg, u, colsum, bsum)
+                                : launch_gram_rows<float>(ctx, p, idx, M, w, G, ldg, u, colsum, bsum);
+}
+
 int32_t ciao_gram_cd(ciao_ctx *ctx, int64_t d, int64_t K, const double *G, int64_t ldg, const double *u, const double *inv, const double *tau,
                      double *X, int64_t ldx, double tol, int32_t max_sweeps, double *R, int64_t ldr, double *stat)
 {

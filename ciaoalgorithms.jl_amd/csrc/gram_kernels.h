@@ -126,19 +126,51 @@ constexpr size_t gram_lds_bytes() { return (size_t)2 * 2 * GRAM_KC * GRAM_PITCH 
 // order of addition is the same: the same bits.
 template <typename T>
 struct Weighted {};
+// The row-list instantiations (ciao_gram_rows): gram_partial_kernel<Indexed<TT>>, TT = T or Weighted<T>, is the same
+// kernel text over a LIST of rows, a.idx = M int64 row numbers.  List position m plays the part of the row number everywhere: a.N = M, the
+// plan is gram_plan(M, d), partitions are ranges of positions, and the weight (Weighted) is read at the position.  Only two addresses
+// change: the panel row of position m is row idx[m] of A, and b is read at idx[m].  Records, final kernels and the order of addition are
+// the ones above, so the outputs are the bits of the unindexed kernel on the gathered copy A[idx], b[idx].
+//   The rows a WAVE parks in one chunk are wave-uniform (fp64: chunk q = 256 i + tid is row 4 i + wave; fp32: rows 8 i + 2 wave and + 1,
+// by lane half), so their indices are scalar LOADS into SGPRs -- NLD * RPW of them a wave and chunk, held as the row's offset idx * ld --
+// fetched TWO chunks ahead, after the MFMA loop of the chunk before the one whose panel loads use them: the loads' wait is the one in
+// front of the barrier, and no wave meets an index before its MFMAs.  The augmented wave, which needs b at the chunk's 16 rows, loads
+// ONE entry a lane at the same point and passes it between lanes where it is used (see arow below): two VGPRs that stay put through the
+// MFMA loop, and with weights one more of validity bits.  Positions are clamped into the partition (nothing beyond idx[M - 1] is read).
+//   An entry outside [0, rows) is a row that does not exist: no load is issued for it and it is 0 in both operands, the ones of the
+// augmented column included.  Context.gram(rows=) refuses such a list before any launch; the predicate is here so that the raw entry
+// point cannot read out of bounds.
+template <typename TT>
+struct Indexed {};
 template <typename TT>
 struct GramElem {
     using type = TT;
+    using base = TT;
     static constexpr bool weighted = false;
+    static constexpr bool indexed = false;
 };
 template <typename T>
 struct GramElem<Weighted<T>> {
     using type = T;
+    using base = Weighted<T>;
     static constexpr bool weighted = true;
+    static constexpr bool indexed = false;
+};
+template <typename TT>
+struct GramElem<Indexed<TT>> {
+    using type = typename GramElem<TT>::type;
+    using base = TT;   // whose final kernel adds the records
+    static constexpr bool weighted = GramElem<TT>::weighted;
+    static constexpr bool indexed = true;
 };
 template <typename T>
 struct GramArgs<Weighted<T>> : GramArgs<T> {
     const double *w;   // N doubles, 8-byte aligned
+};
+template <typename TT>
+struct GramArgs<Indexed<TT>> : GramArgs<TT> {   // N = M, the length of the list; w (Weighted): M doubles, by position
+    const int64_t *idx;   // M row numbers, 8-byte aligned
+    int64_t rows;         // the rows A has: an entry outside [0, rows) is a row that does not exist
 };
 
 template <typename TT>
@@ -146,6 +178,7 @@ __global__ void __launch_bounds__(GRAM_BLOCK) gram_partial_kernel(GramArgs<TT> a
 {
     using T = typename GramElem<TT>::type;
     constexpr bool WEIGHTED = GramElem<TT>::weighted;
+    constexpr bool INDEXED = GramElem<TT>::indexed;
     using M = MfmaOf<double>;
     using Acc = typename M::acc;
     constexpr int VEC = 16 / (int)sizeof(T);
@@ -155,6 +188,8 @@ __global__ void __launch_bounds__(GRAM_BLOCK) gram_partial_kernel(GramArgs<TT> a
     constexpr int NLD = GRAM_KC * CPR / GRAM_BLOCK;       // chunks per thread and panel
     constexpr int PANEL = GRAM_KC * GRAM_PITCH;           // doubles of one parked panel
     static_assert(NLD >= 1 && NLD * GRAM_BLOCK == GRAM_KC * CPR, "panel layout");
+    constexpr int RPW = WAVE / CPR;                       // (INDEXED) rows of which one wave holds chunks in one load: 1 (fp64) or 2 (fp32)
+    static_assert(RPW >= 1 && RPW <= 2 && RPW * CPR == WAVE, "a wave's chunks of one load lie in one or two rows");
     extern __shared__ __attribute__((aligned(16))) unsigned char gram_raw[];
     double *lds = reinterpret_cast<double *>(gram_raw);   // [2 buffers][panel I, panel J][KC][PITCH]
     const int tid = threadIdx.x;
@@ -182,9 +217,71 @@ __global__ void __launch_bounds__(GRAM_BLOCK) gram_partial_kernel(GramArgs<TT> a
     const int64_t r_hi = r_lo + a.per < a.N ? r_lo + a.per : a.N;
     const int64_t ci0 = (int64_t)ib * GRAM_T, cj0 = (int64_t)jb * GRAM_T;
 
+    // (INDEXED) the rows of one chunk.  ri[i][s], wave-uniform, for the rows this wave parks: the row's offset idx[m] * ld in elements, or
+    // -1 where the position lies beyond the partition or the entry names no row -- scalar loads at positions clamped into the partition.
+    // arow: the augmented wave's, lane (c, h) holding the raw entry at position 4 (c & 3) + h (clamped) -- ONE vector load a lane and chunk,
+    // issued after the MFMA loop and first used at the top of the next iteration, where the lane that needs position 4 ks + h takes it
+    // from lane (ks, h).  It stays in its two registers through the loop: a register that the MFMA loop reused while the load may be in
+    // flight would cost every wave a wait for its loads in front of its MFMAs.
+    int64_t ri[NLD][RPW] = {}, arow = 0;
+    auto row_at = [&](int64_t pos) -> int64_t {
+        int64_t r = -1;
+        if constexpr (INDEXED) {
+            const int64_t v = a.idx[pos < r_hi ? pos : r_hi - 1];
+            r = (pos < r_hi && (uint64_t)v < (uint64_t)a.rows) ? v * a.ld : -1;
+        }
+        return r;
+    };
+    auto exists = [&](int64_t r) -> bool {   // of an entry: 0 <= r < rows, one compare
+        if constexpr (INDEXED)
+            return (uint64_t)r < (uint64_t)a.rows;
+        else
+            return true;
+    };
+    auto fetch_rows = [&](int64_t t0) {
+#pragma unroll
+        for (int i = 0; i < NLD; ++i)
+#pragma unroll
+            for (int s = 0; s < RPW; ++s) ri[i][s] = row_at(t0 + i * (GRAM_BLOCK / CPR) + w * RPW + s);
+        if (augwave) {
+            const int64_t pos = t0 + 4 * (c & 3) + h;
+            if constexpr (INDEXED) arow = a.idx[pos < r_hi ? pos : r_hi - 1];
+        }
+    };
     // one panel of the chunk at t0, staged in registers: chunk q = 256 i + tid is chunk q % CPR of row q / CPR
     Vld stI[NLD], stJ[NLD];
     auto load_panel = [&](Vld(&st)[NLD], int64_t c0, int64_t t0) {
+        if constexpr (INDEXED) {   // the rows are ri[][] (fetched for this t0); `whole` is uniform in the WAVE here
+            bool whole = a.vec16 && c0 + GRAM_T <= a.d;
+#pragma unroll
+            for (int i = 0; i < NLD; ++i)
+#pragma unroll
+                for (int s = 0; s < RPW; ++s) whole = whole && ri[i][s] >= 0;
+            if (whole) {
+#pragma unroll
+                for (int i = 0; i < NLD; ++i) {
+                    const int64_t off0 = ri[i][0], off1 = ri[i][RPW - 1];
+                    const int64_t off = (RPW == 2 && (lane & CPR)) ? off1 : off0;
+                    st[i] = *reinterpret_cast<const Vld *>(a.A + off + (c0 + (lane % CPR) * VEC));
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < NLD; ++i) {
+                    const int64_t off0 = ri[i][0], off1 = ri[i][RPW - 1];
+                    const int64_t off = (RPW == 2 && (lane & CPR)) ? off1 : off0;
+                    const bool have = off >= 0;
+                    const int64_t col = c0 + (lane % CPR) * VEC;
+                    const T *src = a.A + off + col;
+                    if (a.vec16 && have && col + VEC <= a.d) {
+                        st[i] = *reinterpret_cast<const Vld *>(src);
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < VEC; ++e) st[i][e] = (have && col + e < a.d) ? src[e] : T(0);
+                    }
+                }
+            }
+            return;
+        }
         const bool whole = a.vec16 && t0 + GRAM_KC <= r_hi && c0 + GRAM_T <= a.d;   // (uniform in the workgroup)
         if (whole) {
 #pragma unroll
@@ -252,7 +349,34 @@ __global__ void __launch_bounds__(GRAM_BLOCK) gram_partial_kernel(GramArgs<TT> a
     // (WEIGHTED: and its weighted twin [w b, w, 0 ... 0])
     double augn[GRAM_KC / 4] = {}, aug[GRAM_KC / 4];
     double augwn[GRAM_KC / 4] = {}, augw[GRAM_KC / 4] = {};
+    // (INDEXED, WEIGHTED) which of this lane's 4 positions of the chunk load_aug last loaded name an existing row: bit ks for position
+    // 4 ks + h.  (The operands of a chunk are made before load_aug runs for the next one.)
+    uint32_t amask = 0;
     auto load_aug = [&](int64_t t0) {
+        if constexpr (INDEXED) {   // the rows are in arow (fetched for this t0); b at the row, the weight at the position
+            if constexpr (WEIGHTED) amask = 0;
+#pragma unroll
+            for (int ks = 0; ks < GRAM_KC / 4; ++ks) {
+                const int64_t pos = t0 + 4 * ks + h;
+                const int src = (16 * h + ks) * 4;   // lane (ks, h)
+                const int64_t row = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)((uint64_t)arow >> 32)) << 32) |
+                                              (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)(uint32_t)arow));
+                const bool have = pos < r_hi && exists(row);
+                if constexpr (WEIGHTED) amask |= have ? 1u << ks : 0u;
+                if constexpr (WEIGHTED) {   // loads without branches: b at row 0 where the row does not exist (its value is not used)
+                    augn[ks] = (double)a.b[have ? row : 0];
+                    augwn[ks] = a.w[pos < r_hi ? pos : r_hi - 1];
+                } else {
+                    double v = 0.0;
+                    if (have) {
+                        if (c == 0) v = (double)a.b[row];
+                        if (c == 1) v = 1.0;
+                    }
+                    augn[ks] = v;
+                }
+            }
+            return;
+        }
 #pragma unroll
         for (int ks = 0; ks < GRAM_KC / 4; ++ks) {
             const int64_t row = t0 + 4 * ks + h;
@@ -276,10 +400,12 @@ __global__ void __launch_bounds__(GRAM_BLOCK) gram_partial_kernel(GramArgs<TT> a
     for (int i = 0; i < 16; ++i) acc[i] = Acc(0.0);
 
     if (r_lo < r_hi) {
+        if constexpr (INDEXED) fetch_rows(r_lo);
         if constexpr (WEIGHTED) load_weights(r_lo);
         load_panel(stI, ci0, r_lo);
         if (!diag) load_panel(stJ, cj0, r_lo);
         if (augwave) load_aug(r_lo);
+        if constexpr (INDEXED) fetch_rows(r_lo + GRAM_KC);
         park_panel(stI, lds);
         if constexpr (WEIGHTED) {
             if (diag)
@@ -297,7 +423,7 @@ __global__ void __launch_bounds__(GRAM_BLOCK) gram_partial_kernel(GramArgs<TT> a
 #pragma unroll
         for (int ks = 0; ks < GRAM_KC / 4; ++ks) {
             if constexpr (WEIGHTED) {   // [b, 1, 0 ... 0] and [w b, w, 0 ... 0] of row t0 + 4 ks + h from the raw loads of a chunk ago; 0 where the row does not exist
-                const bool have = augwave && t0 + 4 * ks + h < r_hi;
+                const bool have = augwave && (INDEXED ? (amask >> ks & 1u) != 0 : t0 + 4 * ks + h < r_hi);
                 aug[ks] = have ? (c == 0 ? augn[ks] : c == 1 ? 1.0 : 0.0) : 0.0;
                 augw[ks] = have && c < 2 ? augwn[ks] * aug[ks] : 0.0;
             } else {
@@ -340,6 +466,8 @@ __global__ void __launch_bounds__(GRAM_BLOCK) gram_partial_kernel(GramArgs<TT> a
                 acc[8] = M::mma(aug[ks], WEIGHTED ? augw[ks] : aug[ks], acc[8]);
             }
         }
+        // the rows of the chunk after the next: used by the next iteration's loads, waited for at the barrier
+        if constexpr (INDEXED) fetch_rows(t0 + 2 * GRAM_KC);
         if (next) {
             double *dst = lds + (size_t)(buf ^ 1) * 2 * PANEL;
             park_panel(stI, dst);

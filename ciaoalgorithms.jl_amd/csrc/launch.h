@@ -183,6 +183,10 @@ int32_t launch_gram(ciao_ctx *ctx, const ciao_problem *p, double *G, int64_t ldg
 template <typename T>
 int32_t launch_gram_weighted(ciao_ctx *ctx, const ciao_problem *p, const double *w, double *G, int64_t ldg, double *u, double *colsum,
                              double *bsum);
+// ... over a list of rows (ciao_gram_rows): idx = M >= 1 device int64 row numbers, w = M device doubles or NULL; the plan is gram_plan(M, d)
+template <typename T>
+int32_t launch_gram_rows(ciao_ctx *ctx, const ciao_problem *p, const int64_t *idx, int64_t M, const double *w, double *G, int64_t ldg, double *u,
+                         double *colsum, double *bsum);
 
 // Coordinate descent on a Gram matrix (gramcd_kernels.h; ciao_gram_cd): K models, one workgroup each; arguments already checked.
 // Defined in gramcd.hip.

@@ -1,0 +1,125 @@
+"""K-fold cross-validation of the lasso path in d-space, at ONE pass over A in total.
+
+The statistics of fold f come from a Gram pass over that fold's row list (Context.gram(rows=): the cost of the rows touched, so the folds
+together cost one pass); the training statistics of fold f are the sum of the other folds' (gram.add_stats); the K models of a fold come
+from gram.lasso_cd / gram.lasso_path on them; the held-out error of a model is a quadratic form in the fold's own statistics (gram.mse).
+After the Gram calls nothing reads A.
+
+    res = lasso_cv(ctx, F, mus, folds=5, seed=0)
+    res.mse[f, k]; res.mean; res.stderr; mus[res.best]; mus[res.one_se]; res.path.x[res.one_se]
+
+LeastSquares rows only (logistic statistics are refused, as GramLasso refuses them); the columns are not standardised inside the folds.
+solvers.py imports nothing from here.
+"""
+from __future__ import annotations
+
+import math
+from typing import NamedTuple
+
+from . import _lib as L
+from .gram import GramStats, _need_ls, add_stats, gram_stats, host_gram_stats, lasso_path, mse
+
+
+class CVResult(NamedTuple):
+    mus: list           # the K l1 weights, as given
+    mse: object         # (folds, K) float64 CPU tensor: held-out mean squared residual of model k on fold f
+    mean: object        # (K,) the mean over the folds
+    stderr: object      # (K,) std(ddof=1) / sqrt(folds)
+    best: int           # argmin of the mean; a NaN never wins, ties go to the smaller index
+    one_se: int         # the index of the largest mu whose mean is <= mean[best] + stderr[best]
+    path: object        # gram.LassoPath refitted on the sum of all folds, for every mu
+    floor: float        # the largest rounding floor (gram.mse) met in the table: differences of mse below it mean nothing
+
+
+def fold_lists(N, folds, seed=0, device="cpu"):
+    """`folds` sorted int64 lists that partition 0 .. N-1: a seeded torch permutation (drawn on the CPU, so the folds do not depend on the
+    device) cut into near-equal parts -- the first N mod folds parts hold one row more -- each sorted ascending for locality."""
+    import torch
+    N, folds = int(N), int(folds)
+    if not 2 <= folds <= N:
+        raise ValueError(f"fold_lists needs 2 <= folds <= N (got folds={folds}, N={N})")
+    g = torch.Generator(device="cpu")
+    g.manual_seed(int(seed))
+    perm = torch.randperm(N, generator=g, dtype=torch.int64)
+    base, extra = divmod(N, folds)
+    out, lo = [], 0
+    for f in range(folds):
+        hi = lo + base + (1 if f < extra else 0)
+        out.append(torch.sort(perm[lo:hi]).values.contiguous().to(device))
+        lo = hi
+    return out
+
+
+def fold_stats(ctx, F, lists):
+    """One GramStats per list: len(lists) calls of gram_stats(ctx, F, rows=list).  With ctx=None and F = (A, b) numpy arrays (optionally
+    (A, b, lam)) the statistics come from host_route.host_gram instead, as CPU tensors."""
+    if ctx is None:
+        import numpy as np
+        A, b = F[0], F[1]
+        lam = float(F[2]) if len(F) > 2 else 1.0
+        return [host_gram_stats(A, b, lam=lam, rows=np.asarray(r.cpu() if hasattr(r, "cpu") else r, dtype=np.int64)) for r in lists]
+    return [gram_stats(ctx, F, rows=r) for r in lists]
+
+
+def choose(mus, mean, stderr):
+    """(best, one_se) from the table's column means by their definitions."""
+    best, val = -1, math.inf
+    for k, v in enumerate(mean):
+        if v == v and (best < 0 or v < val):
+            best, val = k, v
+    if best < 0:
+        raise ValueError("lasso_cv: every model's mean error is NaN")
+    se = stderr[best]
+    bound = val + (se if se == se else 0.0)
+    one_se = best
+    for k, v in enumerate(mean):
+        if v == v and v <= bound and mus[k] > mus[one_se]:
+            one_se = k
+    return best, one_se
+
+
+def lasso_cv_from_stats(stats_f, mus, gap=1e-6, method="cd", ctx=None) -> CVResult:
+    """Cross-validation from the folds' statistics alone: pure d-space, on whatever device the statistics live (device statistics with
+    method="cd" need the Context to launch on, as gram.lasso_cd).  For each fold f: the training statistics are add_stats of the other
+    folds in fold order, the K models come from lasso_path(method=) on them with the gap asked for, and the held-out errors from
+    mse(stats_f[f], X).  The table itself is formed on the HOST in float64 (a d x d x K product per fold), so that it does not depend on
+    the device the statistics live on."""
+    import torch
+    stats_f = list(stats_f)
+    if len(stats_f) < 2:
+        raise ValueError("lasso_cv_from_stats needs at least two folds")
+    for s in stats_f:
+        if not isinstance(s, GramStats):
+            raise TypeError("lasso_cv_from_stats takes a list of gram.GramStats")
+        _need_ls(s, "lasso_cv")
+    mus = [float(m) for m in mus]
+    K = len(mus)
+    if K < 1 or any(not (m > 0 and math.isfinite(m)) for m in mus):
+        raise ValueError("lasso_cv needs at least one l1 weight, every one > 0 and finite")
+    nf = len(stats_f)
+    table = torch.empty((nf, K), dtype=torch.float64)
+    floor = 0.0
+    for f in range(nf):
+        train = add_stats([s for g, s in enumerate(stats_f) if g != f])
+        fit = lasso_path(train, mus, gap=gap, method=method, ctx=ctx)
+        X = torch.stack([x.double().cpu() for x in fit.x], dim=1)
+        v, fl = mse(stats_f[f].to("cpu"), X)
+        table[f] = v
+        fl = fl[fl == fl]
+        if fl.numel():
+            floor = max(floor, float(fl.max()))
+    mean = table.mean(0)
+    stderr = table.std(0, unbiased=True) / math.sqrt(nf)
+    best, one_se = choose(mus, mean.tolist(), stderr.tolist())
+    path = lasso_path(add_stats(stats_f), mus, gap=gap, method=method, ctx=ctx)
+    return CVResult(mus, table, mean, stderr, best, one_se, path, floor)
+
+
+def lasso_cv(ctx, F, mus, folds=5, seed=0, gap=1e-6, method="cd") -> CVResult:
+    """K-fold cross-validation of the lasso path over the rows of F at one pass over A in total: fold_lists(F.N, folds, seed), then
+    fold_stats (one Gram pass per fold over that fold's row list), then lasso_cv_from_stats.  F: a device.PackedF of LeastSquares rows."""
+    from .device import PackedF
+    if not isinstance(F, PackedF) or F.loss != L.LOSS_LS:
+        raise L.CiaoError(L.ERR_ARG, "lasso_cv covers device.PackedF problems of LeastSquares rows (logistic cross-validation is not built)")
+    lists = fold_lists(F.N, folds, seed, device=F.A.device)
+    return lasso_cv_from_stats(fold_stats(ctx, F, lists), mus, gap=gap, method=method, ctx=ctx)

@@ -599,7 +599,7 @@ class Context:
         return out
 
     # -- Gram statistics (gram.py) -------------------------------------------------------------------
-    def gram(self, F, G=None, u=True, colsum=True, bsum=True, weights=None):
+    def gram(self, F, G=None, u=True, colsum=True, bsum=True, weights=None, rows=None, check_rows=True):
         """(G, u, colsum, bsum) with G = A'A (d x d), u = A'b, colsum = A'1 and bsum = (sum b, sum b^2) over the N local rows of F
         (include/ciao_hip.h: ciao_gram) -> device float64 tensors whatever F's dtype is; fp32 rows give the bits their .double() copy
         gives.  G: a row-major float64 device matrix of d rows (any row stride >= d; columns beyond d are not written), a fresh one by
@@ -612,15 +612,29 @@ class Context:
         section 8.13) -> G = A'diag(w)A, u = A'(w b), colsum = A'w and bsum = (sum w b, sum w b^2, sum w): THREE elements then.  One
         operand of every product is w_n times an element, rounded once, the other the raw element: any finite weight, negative ones
         included; w = 1 gives the unweighted bits; 0/1 weights the statistics of a row subset.  A zero weight does not mask a
-        non-finite element (0 inf = NaN)."""
+        non-finite element (0 inf = NaN).
+
+        rows: a contiguous int64 device vector of M local row numbers, at any 8-byte alignment (a slice of a longer tensor works), in
+        any order, repeats allowed (include/ciao_hip.h: ciao_gram_rows) -> the statistics of A[rows], b[rows] at
+        the cost of the M rows touched, BIT FOR BIT what gram() gives on that gathered copy.  weights then has M elements, one per list
+        position.  check_rows: take min and max of the list on the device and raise ValueError before any launch where an entry lies
+        outside [0, N) (one synchronisation); False skips it (the kernel then treats such an entry as a row of zeros)."""
         if isinstance(F, PackedSepQuad):
             raise L.CiaoError(L.ERR_ARG, "the Gram matrix exists for LeastSquares / logistic rows, not for the sharing problem")
         dev = f"cuda:{self.device}"
         d = F.d
+        if rows is not None and not (isinstance(rows, torch.Tensor) and rows.is_cuda and rows.device.index == self.device
+                                     and rows.dtype == torch.int64 and rows.dim() == 1 and rows.is_contiguous()):
+            raise ValueError(f"rows: need a contiguous int64 vector of row numbers on cuda:{self.device}")
+        nw = F.N if rows is None else int(rows.shape[0])
         if weights is not None and not (isinstance(weights, torch.Tensor) and weights.is_cuda and weights.device.index == self.device
-                                        and weights.dtype == torch.float64 and weights.dim() == 1 and weights.shape[0] == F.N
+                                        and weights.dtype == torch.float64 and weights.dim() == 1 and weights.shape[0] == nw
                                         and weights.is_contiguous()):
-            raise ValueError(f"weights: need a contiguous float64 vector of {F.N} elements on cuda:{self.device}")
+            raise ValueError(f"weights: need a contiguous float64 vector of {nw} elements on cuda:{self.device}")
+        if rows is not None and check_rows and nw > 0:
+            lo, hi = (int(v) for v in torch.aminmax(rows))
+            if lo < 0 or hi >= F.N:
+                raise ValueError(f"rows: entries must lie in [0, {F.N}) (got min {lo}, max {hi})")
         nb = 2 if weights is None else 3
 
         def fresh(*shape):
@@ -645,7 +659,11 @@ class Context:
                 self._dvec(v, name, n)
                 outs.append(v)
         outp = [None if v is None else _ptr(v) for v in outs]
-        if weights is None:
+        if rows is not None:
+            # (an empty weight vector has no address: any aligned non-NULL one says "weighted", three sums; with M = 0 nothing is read)
+            wp = None if weights is None else (_ptr(weights) if nw > 0 else _ptr(G))
+            L.check(self.lib.ciao_gram_rows(self._h, F.ref, _ptr(rows), nw, wp, _ptr(G), ldg, *outp))
+        elif weights is None:
             L.check(self.lib.ciao_gram(self._h, F.ref, _ptr(G), ldg, *outp))
         else:
             L.check(self.lib.ciao_gram_weighted(self._h, F.ref, _ptr(weights), _ptr(G), ldg, *outp))

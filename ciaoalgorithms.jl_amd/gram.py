@@ -89,7 +89,7 @@ class GramStats(NamedTuple):
         return self._replace(G=G, u=sc * u, colsum=sc * colsum, sum_b=sum_b, sum_bb=sum_bb), scaler
 
 
-def gram_stats(ctx, F, weights=None) -> GramStats:
+def gram_stats(ctx, F, weights=None, rows=None) -> GramStats:
     """One pass over the rows of F (Context.gram) -> GramStats on F's device.  F: a device.PackedF of real LeastSquares or logistic rows
     with d <= 4096; refused on a row-sharded context (the ranks' matrices would have to be added).  Synchronises (the two sums of b
     cross to the host).
@@ -98,7 +98,10 @@ def gram_stats(ctx, F, weights=None) -> GramStats:
     u = A'(w b), colsum = A'w, sum_b = sum w b, sum_bb = sum w b^2, sum_w = sum w.  N stays the row count, so the objective GramLasso
     evaluates is lam / (2 N) sum_i w_i (a_i'x - b_i)^2; GramLasso, lasso_path and mu_max take such statistics as they are (sample
     weights; with 0/1 weights a fold of a cross-validation without copying rows).  Weights of both signs are summed faithfully, but the
-    lasso functions assume G positive semidefinite."""
+    lasso functions assume G positive semidefinite.
+
+    rows: a contiguous int64 device vector of M >= 1 row numbers (Context.gram(rows=)) -> the statistics of
+    A[rows], b[rows] at the cost of the rows touched, with N = M; weights then has M elements."""
     from .device import PackedF
     from .stepsize import _on_stream
     if not isinstance(F, PackedF) or F.loss not in (L.LOSS_LS, L.LOSS_LOGISTIC):
@@ -109,26 +112,74 @@ def gram_stats(ctx, F, weights=None) -> GramStats:
                                      "Gram matrices are not combined")
     if F.N < 1:
         raise L.CiaoError(L.ERR_ARG, "gram_stats needs at least one row (N = 0)")
-    G, u, colsum, bsum = ctx.gram(F, weights=weights)
+    if rows is not None and int(rows.shape[0]) < 1:
+        raise L.CiaoError(L.ERR_ARG, "gram_stats needs at least one row (an empty list)")
+    G, u, colsum, bsum = ctx.gram(F, weights=weights, rows=rows)
     with _on_stream(ctx):
         sb = bsum.cpu()
     ls = F.loss == L.LOSS_LS
-    return GramStats(int(F.N), int(F.d), G, u, colsum, float(sb[0]), float(sb[1]), float(F.lam) if ls else 1.0, "ls" if ls else "logistic",
+    return GramStats(int(F.N) if rows is None else int(rows.shape[0]), int(F.d), G, u, colsum, float(sb[0]), float(sb[1]), float(F.lam) if ls else 1.0, "ls" if ls else "logistic",
                      F.dtype, None if weights is None else float(sb[2]))
 
 
-def host_gram_stats(A, b, lam=1.0, kind="ls", weights=None) -> GramStats:
-    """GramStats from host_route.host_gram on a host matrix (numpy), as CPU torch tensors.  weights: a real N-vector (gram_stats)."""
+def host_gram_stats(A, b, lam=1.0, kind="ls", weights=None, rows=None) -> GramStats:
+    """GramStats from host_route.host_gram on a host matrix (numpy), as CPU torch tensors.  weights: a real N-vector (gram_stats);
+    rows: an integer list of row numbers (gram_stats): the statistics of A[rows], b[rows], N = len(rows)."""
     import numpy as np
     import torch
     from .host_route import host_gram
     if kind not in ("ls", "logistic"):
         raise ValueError(f"kind must be 'ls' or 'logistic' (got {kind!r})")
     A = np.asarray(A)
-    G, u, colsum, bsum = host_gram(A, b, weights)
+    G, u, colsum, bsum = host_gram(A, b, weights, rows)
     dt = torch.float32 if A.dtype == np.float32 else torch.float64
-    return GramStats(A.shape[0], A.shape[1], torch.from_numpy(G), torch.from_numpy(u), torch.from_numpy(colsum), float(bsum[0]), float(bsum[1]),
+    return GramStats(A.shape[0] if rows is None else len(rows), A.shape[1], torch.from_numpy(G), torch.from_numpy(u), torch.from_numpy(colsum), float(bsum[0]), float(bsum[1]),
                      float(lam) if kind == "ls" else 1.0, kind, dt, None if weights is None else float(bsum[2]))
+
+
+def add_stats(stats) -> GramStats:
+    """The statistics of the rows of several disjoint sets together: G, u, colsum, the two sums of b and N added in list order (the
+    training statistics of a cross-validation fold are the sum of the other folds').  The same d, lam, kind and device throughout;
+    weighted statistics are refused (their N is not the weight they carry).  The sums are floating-point sums of the parts: exact where
+    the parts are (integer rows), otherwise within the parts' own rounding."""
+    stats = list(stats)
+    if not stats:
+        raise ValueError("add_stats needs at least one GramStats")
+    s0 = stats[0]
+    for s in stats:
+        if s.sum_w is not None:
+            raise L.CiaoError(L.ERR_ARG, "add_stats takes unweighted statistics (sum_w is set on one of them)")
+        if (s.d, s.lam, s.kind) != (s0.d, s0.lam, s0.kind):
+            raise L.CiaoError(L.ERR_ARG, f"add_stats needs the same d, lam and kind throughout (got {(s.d, s.lam, s.kind)} beside "
+                                         f"{(s0.d, s0.lam, s0.kind)})")
+    G, u, colsum, N, sb, sbb = s0.G, s0.u, s0.colsum, s0.N, s0.sum_b, s0.sum_bb
+    for s in stats[1:]:
+        G, u, colsum, N, sb, sbb = G + s.G, u + s.u, colsum + s.colsum, N + s.N, sb + s.sum_b, sbb + s.sum_bb
+    if len(stats) == 1:
+        G, u, colsum = G.clone(), u.clone(), colsum.clone()
+    return s0._replace(N=N, G=G, u=u, colsum=colsum, sum_b=sb, sum_bb=sbb)
+
+
+def mse(stats: GramStats, X):
+    """(mse, floor): the mean squared residual (1/N) sum_i (a_i'x_k - b_i)^2 = (x_k'G x_k - 2 u'x_k + sum b^2) / N of the K columns of X
+    (d x K, or one d-vector) over the rows `stats` were taken from, as one d x d x K product and without a pass over A: the held-out
+    error of a model on a fold.  floor: GramLasso.value_floor on the same scale, 4 * 2^-53 (x'Gx + 2 |u'x| + sum b^2) / N -- what the
+    rounding of the three terms can amount to; differences of mse below it mean nothing.  LeastSquares statistics, unweighted."""
+    import torch
+    _need_ls(stats, "mse")
+    if stats.sum_w is not None:
+        raise L.CiaoError(L.ERR_ARG, "mse takes unweighted statistics")
+    if not isinstance(X, torch.Tensor):
+        X = torch.as_tensor(X)
+    X = X.to(device=stats.G.device, dtype=torch.float64)
+    one = X.dim() == 1
+    if one:
+        X = X[:, None]
+    q = (X * (stats.G @ X)).sum(0)
+    l = (stats.u[:, None] * X).sum(0)
+    v = (q - 2.0 * l + stats.sum_bb) / stats.N
+    fl = 4.0 * EPS * (q + 2.0 * l.abs() + stats.sum_bb) / stats.N
+    return (float(v[0]), float(fl[0])) if one else (v, fl)
 
 
 def smoothness_exact(stats: GramStats) -> float:

@@ -464,7 +464,7 @@ def host_col_moments(A, shift=None):
     return np.sum(t, axis=0), np.sum(t * t, axis=0)
 
 
-def host_gram(A, b, weights=None):
+def host_gram(A, b, weights=None, rows=None):
     """The Gram statistics of ciao_gram in numpy (float64) -> (G, u, colsum, bsum): G = A'A, u = A'b, colsum = A'1, bsum = [sum b,
     sum b^2].  The products are what the device forms (float32 data is exact in float64, and so is every product of two of them); the
     order of addition is numpy's, so the two agree to (N + 8) 2^-53 sum_n |a_ni a_nj| per entry, and bitwise where every sum is exact.
@@ -473,10 +473,20 @@ def host_gram(A, b, weights=None):
     As on the device ONE operand of every product carries the weight, rounded once: G[i][j] = sum_n a_ni (w_n a_nj) for i <= j and the
     other triangle is its mirror; u[j] = sum_n a_nj (w_n b_n); colsum[j] = sum_n a_nj w_n; sum w b^2 = sum_n b_n (w_n b_n).  No square
     root of w: any finite weight, w = 1 gives the unweighted result bit for bit, a zero weight does not mask a non-finite element.
-    The bound grows to (N + 10) 2^-53 sum_n |w_n a_ni a_nj|."""
+    The bound grows to (N + 10) 2^-53 sum_n |w_n a_ni a_nj|.
+
+    rows: an integer M-vector of row numbers in [0, N), any order, repeats allowed (ciao_gram_rows) -> the statistics of the gathered
+    copy A[rows], b[rows]; weights then has M elements, one per list position.  An empty list gives zeros."""
     A, b = np.asarray(A), np.asarray(b)
     if A.ndim != 2 or np.iscomplexobj(A) or np.iscomplexobj(b) or b.shape != (A.shape[0],):
         raise ValueError("A must be a real N x d matrix and b a real N-vector")
+    if rows is not None:
+        rows = np.asarray(rows)
+        if rows.ndim != 1 or not np.issubdtype(rows.dtype, np.integer):
+            raise ValueError("rows must be an integer vector of row numbers")
+        if rows.size and (rows.min() < 0 or rows.max() >= A.shape[0]):
+            raise ValueError(f"rows: entries must lie in [0, {A.shape[0]})")
+        A, b = A[rows], b[rows]
     A, b = A.astype(np.float64), b.astype(np.float64)
     if weights is None:
         return A.T @ A, A.T @ b, np.sum(A, axis=0), np.array([np.sum(b), np.sum(b * b)])

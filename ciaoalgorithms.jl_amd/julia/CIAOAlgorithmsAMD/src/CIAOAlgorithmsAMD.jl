@@ -539,6 +539,23 @@ function gram_weighted(F::PackedF{R}, w::ROCArray{Float64}; u::Bool = true, cols
     return G, uv, cs, bs
 end
 
+# gram_rows: the statistics of a LIST of rows at the cost of the rows touched (ciao_gram_rows; Python twin: Context.gram(rows=); DESIGN.md
+# section 8.15): gram (w === nothing) or gram_weighted on the gathered copy A[rows], b[rows], bit for bit, without forming it.  rows: M
+# Int64 ZERO-BASED row numbers on the device, any order, repeats allowed (the ABI's numbering; every entry must lie in 0:N-1 -- the caller
+# checks, as Context.gram does); w: M Float64 on the device, one per list position.
+function gram_rows(F::PackedF{R}, rows::ROCArray{Int64}; w::Union{Nothing,ROCArray{Float64}} = nothing, u::Bool = true, colsum::Bool = true,
+                   bsum::Bool = true) where {R}
+    (w === nothing || length(w) == length(rows)) || throw(ArgumentError("gram_rows needs one weight per list position"))
+    d = Int(F.d)
+    G = ROCArray{Float64}(undef, d, d)
+    uv = u ? ROCArray{Float64}(undef, d) : nothing
+    cs = colsum ? ROCArray{Float64}(undef, d) : nothing
+    bs = bsum ? ROCArray{Float64}(undef, w === nothing ? 2 : 3) : nothing
+    check(ccall((:ciao_gram_rows, libciao), Int32, (Ptr{Cvoid}, Ref{CiaoProblem}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                context().h, Ref(cproblem(F)), dptr(rows), Int64(length(rows)), dptr(w), dptr(G), Int64(d), dptr(uv), dptr(cs), dptr(bs)))
+    return G, uv, cs, bs
+end
+
 function gram_stats(F::PackedF{R}) where {R}
     (F.loss == LOSS_LS || F.loss == LOSS_LOGISTIC) || throw(ArgumentError("Gram statistics need real LeastSquares or logistic rows"))
     F.N >= 1 || throw(ArgumentError("Gram statistics need at least one row"))

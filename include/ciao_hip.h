@@ -336,6 +336,22 @@ CIAO_API int32_t ciao_gram(ciao_ctx *ctx, const ciao_problem *p, double *G, int6
  * Workspace: ciao_gram's.  Does not synchronise, except where that workspace has to grow. */
 CIAO_API int32_t ciao_gram_weighted(ciao_ctx *ctx, const ciao_problem *p, const double *w, double *G, int64_t ldg, double *u, double *colsum,
                                     double *bsum);
+/* EXTENSION beyond the reference: the statistics of a LIST of rows at the cost of the rows touched -- ciao_gram / ciao_gram_weighted over
+ * the gathered matrix A[idx], b[idx] without forming it.  DESIGN.md section 8.15.  idx: a device vector of M int64 row numbers (LOCAL rows
+ * on a row-sharded context) at any 8-byte-aligned address, in any order, repeats allowed (a bootstrap resample, a random fold); nothing
+ * beyond idx[M-1] is read.  List position m plays the part the row number plays in ciao_gram: the panel row and b are read at idx[m], the
+ * weight (w: M device DOUBLES at any 8-byte-aligned address, or NULL for the unweighted statistics) at the POSITION m, so a bootstrap's
+ * counts or w[idx] go in directly; nothing beyond w[M-1] is read.  bsum: 2 device doubles without w, 3 with it; G, ldg, u, colsum and the
+ * NULL rule as ciao_gram.  Plan, tiles, workspace, order of addition and the final kernels are ciao_gram's for (M, d): the outputs are BIT
+ * FOR BIT those of ciao_gram (with w: of ciao_gram_weighted) on the gathered copy, for every ld, base and alignment of A, idx and w;
+ * idx = 0 .. N-1 gives ciao_gram's bits on A itself.  A is read only: the rows named by the list, columns [0, d) of them.
+ * An entry outside [0, N) names a row that does not exist: the kernel issues no load for it and the row is zero in both operands (the
+ * ones of the augmented column included, so it counts in no sum); Context.gram(rows=) refuses such a list BEFORE any launch -- the
+ * predicate is there so that this raw entry point cannot read out of bounds.  Refused with CIAO_ERR_ARG and nothing launched: a NULL or
+ * misaligned idx (M = 0 aside), M < 0, a misaligned w, and everything ciao_gram refuses.  M = 0: every output is set to zero, no kernel is
+ * launched.  Workspace: ciao_gram's.  Does not synchronise, except where that workspace has to grow. */
+CIAO_API int32_t ciao_gram_rows(ciao_ctx *ctx, const ciao_problem *p, const int64_t *idx, int64_t M, const double *w, double *G, int64_t ldg,
+                                double *u, double *colsum, double *bsum);
 /* EXTENSION beyond the reference: cyclic coordinate descent with covariance updates for the lasso on a Gram matrix (glmnet's inner loop),
  * K models in one launch, one workgroup each.  DESIGN.md section 8.14.  Everything is DOUBLE and on the device:
  *     min_x (c/2)(x'G x - 2 u'x + const) + mu_k ||x||_1,   tau[k] = mu_k / c
