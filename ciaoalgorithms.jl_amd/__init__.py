@@ -12,6 +12,7 @@ The directory name contains a dot, so it is loaded under the importable alias `c
     parallel.py      row sharding + torch.distributed (RCCL) all-reduce hook
     gram.py          Gram statistics (plain and with a weight per row) and what follows from them in d-space: GramLasso, lasso_path, lasso_cd (coordinate descent: ciao_gram_cd)
     cv.py            K-fold cross-validation of the lasso path in d-space: the folds' Gram statistics from passes over row lists (ciao_gram_rows)
+                     and of the l1-logistic path (logistic_cv): every fold a problem on a row list (ciao_list_dots, ciao_list_combine)
     newton.py        a proximal Newton path for l1-logistic rows on the weighted Gram pass (DeviceRows / HostRows)
     julia/           the Julia wrapper module (written against the same ABI; cannot run in this image)
 Importing this package does not need a GPU; creating a Context does.  There is no CPU fallback.

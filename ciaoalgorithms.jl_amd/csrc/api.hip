@@ -1853,6 +1853,44 @@ int32_t ciao_gram_rows(ciao_ctx *ctx, const ciao_problem *p, const int64_t *idx,
                                 : launch_gram_rows<float>(ctx, p, idx, M, w, G, ldg, u, colsum, bsum);
 }
 
+// what ciao_list_dots and ciao_list_combine refuse alike (v = x or c)
+static int32_t check_list(ciao_ctx *ctx, const ciao_problem *p, const char *name, const int64_t *idx, int64_t M)
+{
+    CIAO_REQUIRE(M >= 0, "%s: the length of the row list, M=%lld, is negative", name, (long long)M);
+    CIAO_TRY(check_problem(ctx, p));
+    CIAO_REQUIRE(p->loss != CIAO_LOSS_LS_COMPLEX, "%s covers real problems only (complex T: rows of (re, im) pairs)", name);
+    CIAO_REQUIRE(p->loss != CIAO_LOSS_ZERO, "%s needs data rows (Zero() terms have no matrix A)", name);
+    CIAO_REQUIRE(p->d <= 4096, "%s takes rows of at most 4096 elements (got d=%lld)", name, (long long)p->d);
+    CIAO_REQUIRE(idx || M == p->N, "%s: without a row list (idx = NULL) M must be the number of rows, N=%lld (got M=%lld)", name,
+                 (long long)p->N, (long long)M);
+    CIAO_REQUIRE((reinterpret_cast<uintptr_t>(idx) & 7u) == 0, "%s: the row list idx is not aligned to 8 bytes", name);
+    return CIAO_OK;
+}
+
+int32_t ciao_list_dots(ciao_ctx *ctx, const ciao_problem *p, const int64_t *idx, int64_t M, const void *x, double *out)
+{
+    CIAO_REQUIRE(ctx && p && x && out, "ciao_list_dots: the context, the problem, x or the output vector is NULL");
+    CIAO_ENTER(ctx);
+    CIAO_TRY(check_list(ctx, p, "ciao_list_dots", idx, M));
+    CIAO_REQUIRE((reinterpret_cast<uintptr_t>(out) & 7u) == 0, "ciao_list_dots: the output vector is not aligned to 8 bytes");
+    if (M == 0) return CIAO_OK;   // an empty list: there is nothing to write, nothing is launched
+    return p->dtype == CIAO_F64 ? launch_listdot<double>(ctx, p, idx, M, x, out) : launch_listdot<float>(ctx, p, idx, M, x, out);
+}
+
+int32_t ciao_list_combine(ciao_ctx *ctx, const ciao_problem *p, const int64_t *idx, int64_t M, const double *c, double *out)
+{
+    CIAO_REQUIRE(ctx && p && c && out, "ciao_list_combine: the context, the problem, c or the output vector is NULL");
+    CIAO_ENTER(ctx);
+    CIAO_TRY(check_list(ctx, p, "ciao_list_combine", idx, M));
+    CIAO_REQUIRE(((reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(out)) & 7u) == 0,
+                 "ciao_list_combine: c or the output vector is not aligned to 8 bytes");
+    if (M == 0) {   // an empty list: the sum of no term, nothing is launched
+        CIAO_HIP(hipMemsetAsync(out, 0, (size_t)p->d * sizeof(double), ctx->stream));
+        return CIAO_OK;
+    }
+    return p->dtype == CIAO_F64 ? launch_listcomb<double>(ctx, p, idx, M, c, out) : launch_listcomb<float>(ctx, p, idx, M, c, out);
+}
+
 int32_t ciao_gram_cd(ciao_ctx *ctx, int64_t d, int64_t K, const double *G, int64_t ldg, const double *u, const double *inv, const double *tau,
                      double *X, int64_t ldx, double tol, int32_t max_sweeps, double *R, int64_t ldr, double *stat)
 {

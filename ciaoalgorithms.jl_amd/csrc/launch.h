@@ -188,6 +188,15 @@ template <typename T>
 int32_t launch_gram_rows(ciao_ctx *ctx, const ciao_problem *p, const int64_t *idx, int64_t M, const double *w, double *G, int64_t ldg, double *u,
                          double *colsum, double *bsum);
 
+// A matrix-vector product and its adjoint over a list of rows (list_kernels.h; ciao_list_dots, ciao_list_combine): idx = M >= 1 device
+// int64 row numbers, or NULL (position = row, M = N).  launch_listdot: out[m] = a_{idx[m]}'x, M device doubles, x = d elements of the
+// rows' type; launch_listcomb: out[j] = sum_m c[m] A[idx[m], j], d device doubles, the partial d-vectors go to ctx->partial (grown
+// here).  Specialised in list_f32.hip / list_f64.hip.
+template <typename T>
+int32_t launch_listdot(ciao_ctx *ctx, const ciao_problem *p, const int64_t *idx, int64_t M, const void *x, double *out);
+template <typename T>
+int32_t launch_listcomb(ciao_ctx *ctx, const ciao_problem *p, const int64_t *idx, int64_t M, const double *c, double *out);
+
 // Coordinate descent on a Gram matrix (gramcd_kernels.h; ciao_gram_cd): K models, one workgroup each; arguments already checked.
 // Defined in gramcd.hip.
 int32_t launch_gram_cd(ciao_ctx *ctx, int64_t d, int64_t K, const double *G, int64_t ldg, const double *u, const double *inv, const double *tau,

@@ -8,7 +8,16 @@ After the Gram calls nothing reads A.
     res = lasso_cv(ctx, F, mus, folds=5, seed=0)
     res.mse[f, k]; res.mean; res.stderr; mus[res.best]; mus[res.one_se]; res.path.x[res.one_se]
 
-LeastSquares rows only (logistic statistics are refused, as GramLasso refuses them); the columns are not standardised inside the folds.
+lasso_cv: LeastSquares rows only (logistic statistics are refused, as GramLasso refuses them); the columns are not standardised inside
+the folds.
+
+Logistic rows have no sufficient statistics, so their cross-validation reads rows -- but only the rows a fold names (DESIGN.md section
+8.16): logistic_cv fits every training fold with newton.logistic_path on DeviceRows(ctx, F, rows=train) (Context.list_dots, list_combine
+and gram(weights=, rows=) over the list, no gathered copy) and scores every model on the held-out list (scoring.score(rows=)).
+
+    res = logistic_cv(ctx, F, mus, folds=5, seed=0)
+    res.loss[f, k]; res.accuracy[f, k]; res.mean; res.stderr; mus[res.one_se]; res.path[res.one_se].x
+
 solvers.py imports nothing from here.
 """
 from __future__ import annotations
@@ -120,6 +129,73 @@ def lasso_cv(ctx, F, mus, folds=5, seed=0, gap=1e-6, method="cd") -> CVResult:
     fold_stats (one Gram pass per fold over that fold's row list), then lasso_cv_from_stats.  F: a device.PackedF of LeastSquares rows."""
     from .device import PackedF
     if not isinstance(F, PackedF) or F.loss != L.LOSS_LS:
-        raise L.CiaoError(L.ERR_ARG, "lasso_cv covers device.PackedF problems of LeastSquares rows (logistic cross-validation is not built)")
+        raise L.CiaoError(L.ERR_ARG, "lasso_cv covers device.PackedF problems of LeastSquares rows (logistic cross-validation is not built "
+                                     "here: cv.logistic_cv)")
     lists = fold_lists(F.N, folds, seed, device=F.A.device)
     return lasso_cv_from_stats(fold_stats(ctx, F, lists), mus, gap=gap, method=method, ctx=ctx)
+
+
+class LogisticCVResult(NamedTuple):
+    mus: list           # the K l1 weights, as given
+    loss: object        # (folds, K) float64 CPU tensor: held-out mean log-loss of model k on fold f
+    accuracy: object    # (folds, K) held-out accuracy, 1 - #{y a'x <= 0} / M
+    mean: object        # (K,) the mean of loss over the folds
+    stderr: object      # (K,) std(ddof=1) / sqrt(folds)
+    best: int           # argmin of the mean; a NaN never wins, ties go to the smaller index
+    one_se: int         # the index of the largest mu whose mean is <= mean[best] + stderr[best]
+    path: list          # K newton.NewtonResult: the refit on all rows, for every mu
+    converged: object   # (folds, K) bool: the fold solve ended converged
+
+
+def logistic_cv(ctx, F, mus, folds=5, seed=0, gap=1e-6, subproblem="cd", max_outer=30) -> LogisticCVResult:
+    """K-fold cross-validation of the l1-logistic path without copying rows: fold_lists(F.N, folds, seed); for
+    fold f the training list is the other folds' lists concatenated in fold order and sorted, the K models come from
+    newton.logistic_path(DeviceRows(ctx, F, rows=train), mus, ...) -- in the order given, each solve warm-started from the last -- and
+    the held-out mean log-loss and accuracy of every model from scoring.score(ctx, F, x, rows=lists[f]); the refit on all rows uses
+    DeviceRows(ctx, F).  The table is formed on the host in float64; best / one_se are choose() on the loss means.  Every pass reads
+    only the rows its list names (M / N of a pass over A each); the columns are not standardised inside the folds.
+
+    F: a device.PackedF of logistic rows.  With ctx=None and F = (A, y) numpy arrays the same driver runs on the host: newton.HostRows
+    on gathered copies, the scores from host_route.host_margin_stats."""
+    import torch
+    from .host_route import _score, host_margin_stats
+    from .newton import DeviceRows, HostRows, logistic_path
+    host = ctx is None
+    if host:
+        import numpy as np
+        if not (isinstance(F, (tuple, list)) and len(F) == 2):
+            raise L.CiaoError(L.ERR_ARG, "logistic_cv without a Context takes F = (A, y) numpy arrays")
+        A, y = np.asarray(F[0]), np.asarray(F[1])
+        N = int(A.shape[0])
+    else:
+        from .device import PackedF
+        if not isinstance(F, PackedF) or F.loss != L.LOSS_LOGISTIC:
+            raise L.CiaoError(L.ERR_ARG, "logistic_cv covers device.PackedF problems of logistic rows (LeastSquares rows: cv.lasso_cv)")
+        N = int(F.N)
+    mus = [float(m) for m in mus]
+    K = len(mus)
+    if K < 1 or any(not (m > 0 and math.isfinite(m)) for m in mus):
+        raise ValueError("logistic_cv needs at least one l1 weight, every one > 0 and finite")
+    lists = fold_lists(N, folds, seed, device="cpu" if host else F.A.device)
+    nf = len(lists)
+    loss = torch.empty((nf, K), dtype=torch.float64)
+    acc = torch.empty((nf, K), dtype=torch.float64)
+    conv = torch.empty((nf, K), dtype=torch.bool)
+    for f in range(nf):
+        train = torch.sort(torch.cat([r for g, r in enumerate(lists) if g != f])).values.contiguous()
+        rows = HostRows(A, y, rows=train.numpy()) if host else DeviceRows(ctx, F, rows=train)
+        fit = logistic_path(rows, mus, gap=gap, max_outer=max_outer, subproblem=subproblem)
+        for k, r in enumerate(fit):
+            if host:
+                held = lists[f].numpy()
+                x = np.asarray(r.x, dtype=np.float64)
+                sc = _score("logistic", host_margin_stats("logistic", A[held].astype(np.float64) @ x, y[held], 1.0), len(held))
+            else:
+                from .scoring import score
+                sc = score(ctx, F, r.x, rows=lists[f])
+            loss[f, k], acc[f, k], conv[f, k] = sc.log_loss, sc.accuracy, bool(r.converged)
+    mean = loss.mean(0)
+    stderr = loss.std(0, unbiased=True) / math.sqrt(nf)
+    best, one_se = choose(mus, mean.tolist(), stderr.tolist())
+    path = logistic_path(HostRows(A, y) if host else DeviceRows(ctx, F), mus, gap=gap, max_outer=max_outer, subproblem=subproblem)
+    return LogisticCVResult(mus, loss, acc, mean, stderr, best, one_se, path, conv)

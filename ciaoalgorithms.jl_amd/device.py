@@ -669,6 +669,66 @@ class Context:
             L.check(self.lib.ciao_gram_weighted(self._h, F.ref, _ptr(weights), _ptr(G), ldg, *outp))
         return (G, *outs)
 
+    # -- first-order passes over a list of rows (newton.DeviceRows(rows=), scoring.score(rows=), cv.logistic_cv) --
+    def _row_list(self, F, rows, check_rows, what):
+        """Context.gram's checks of a row list -> (its pointer or None, M)"""
+        if isinstance(F, PackedSepQuad):
+            raise L.CiaoError(L.ERR_ARG, f"{what} exists for LeastSquares / logistic rows, not for the sharing problem")
+        if rows is not None and not (isinstance(rows, torch.Tensor) and rows.is_cuda and rows.device.index == self.device
+                                     and rows.dtype == torch.int64 and rows.dim() == 1 and rows.is_contiguous()):
+            raise ValueError(f"rows: need a contiguous int64 vector of row numbers on cuda:{self.device}")
+        M = F.N if rows is None else int(rows.shape[0])
+        if rows is not None and check_rows and M > 0:
+            lo, hi = (int(v) for v in torch.aminmax(rows))
+            if lo < 0 or hi >= F.N:
+                raise ValueError(f"rows: entries must lie in [0, {F.N}) (got min {lo}, max {hi})")
+        return rows, M
+
+    def _list_out(self, out, n):
+        if out is None:
+            out = torch.empty(n, dtype=torch.float64, device=f"cuda:{self.device}")
+            if self.stream is not None:
+                out.record_stream(self.stream)
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device.index == self.device and out.dtype == torch.float64
+                and out.dim() == 1 and out.is_contiguous() and out.numel() == n):
+            raise ValueError(f"out: need a contiguous float64 vector of {n} elements on cuda:{self.device}")
+        return out
+
+    def list_dots(self, F, x, rows=None, out=None, check_rows=True):
+        """out[m] = a_{rows[m]}'x for the M list positions (include/ciao_hip.h: ciao_list_dots) -> a device
+        float64 M-vector whatever F's dtype is: A[rows] @ x at the cost of the rows touched, BIT FOR BIT what list_dots gives without a
+        list on the gathered copy A[rows]; one row has one bit pattern at every position of every list.  x: a device d-vector of F's
+        dtype.  rows: a contiguous int64 device vector of M local row numbers at any 8-byte alignment, any order, repeats allowed;
+        None: every row in order (M = N).  check_rows: as Context.gram(rows=) -- min and max of the list are taken on the device and
+        an entry outside [0, N) raises ValueError before any launch (one synchronisation); False skips it (the kernel then writes 0 at
+        such a position).  d <= 4096.  Does not synchronise otherwise."""
+        rows, M = self._row_list(F, rows, check_rows, "list_dots")
+        out = self._list_out(out, M)
+        xp = self._vec(x, F, "x")
+        if M == 0:
+            # (an empty list and an empty output have no address: any aligned non-NULL one says "a list"; with M = 0 nothing is read or written)
+            pad = torch.empty(1, dtype=torch.int64, device=f"cuda:{self.device}")
+            L.check(self.lib.ciao_list_dots(self._h, F.ref, None if rows is None else _ptr(pad), 0, xp, _ptr(pad)))
+            return out
+        L.check(self.lib.ciao_list_dots(self._h, F.ref, _ptr(rows), M, xp, _ptr(out)))
+        return out
+
+    def list_combine(self, F, c, rows=None, out=None, check_rows=True):
+        """out[j] = sum_m c[m] A[rows[m], j] (include/ciao_hip.h: ciao_list_combine) -> a device float64
+        d-vector whatever F's dtype is: A[rows]' c at the cost of the rows touched, BIT FOR BIT what list_combine gives without a list
+        on the gathered copy A[rows].  c: a contiguous float64 device M-vector, one coefficient per list position.  rows, check_rows:
+        as list_dots (an entry outside [0, N) contributes no term where the check is skipped).  d <= 4096.  Does not synchronise,
+        except for that check and where the workspace of partial sums has to grow."""
+        rows, M = self._row_list(F, rows, check_rows, "list_combine")
+        if not (isinstance(c, torch.Tensor) and c.is_cuda and c.device.index == self.device and c.dtype == torch.float64 and c.dim() == 1
+                and c.shape[0] == M and c.is_contiguous()):
+            raise ValueError(f"c: need a contiguous float64 vector of {M} elements on cuda:{self.device}")
+        out = self._list_out(out, F.d)
+        # (an empty list / coefficient vector has no address: any aligned non-NULL one will do, with M = 0 nothing is read)
+        L.check(self.lib.ciao_list_combine(self._h, F.ref, _ptr(rows) if (rows is None or M > 0) else _ptr(out), M,
+                                           _ptr(c) if M > 0 else _ptr(out), _ptr(out)))
+        return out
+
     def gram_cd(self, G, u, inv, tau, X, tol, max_sweeps, R=True, stat=None):
         """(X, R, stat): cyclic coordinate descent with covariance updates on a Gram matrix, K models in one launch (include/ciao_hip.h:
         ciao_gram_cd; DESIGN.md section 8.14, with the method to the bit and its numpy mirror).  All float64 device tensors: G (d, d)

@@ -500,6 +500,44 @@ def host_gram(A, b, weights=None, rows=None):
     return G, A.T @ wb, A.T @ w, np.array([np.sum(wb), b @ wb, np.sum(w)])
 
 
+def _list_rows(A, rows):
+    """A (a real N x d matrix) gathered over `rows` as float64, by host_gram's validation of the list; rows=None: every row in order."""
+    A = np.asarray(A)
+    if A.ndim != 2 or np.iscomplexobj(A):
+        raise ValueError("A must be a real N x d matrix")
+    if rows is not None:
+        rows = np.asarray(rows)
+        if rows.ndim != 1 or not np.issubdtype(rows.dtype, np.integer):
+            raise ValueError("rows must be an integer vector of row numbers")
+        if rows.size and (rows.min() < 0 or rows.max() >= A.shape[0]):
+            raise ValueError(f"rows: entries must lie in [0, {A.shape[0]})")
+        A = A[rows]
+    return A.astype(np.float64)
+
+
+def host_list_dots(A, x, rows=None):
+    """ciao_list_dots in numpy (float64): out[m] = a_{rows[m]}'x, an M-vector (rows=None: every row in order).  The products are what
+    the device forms ((double)a * (double)x: exact for float32 data); the order of addition is numpy's, so the two agree to
+    (d + 2) 2^-53 sum_j |a_j x_j| each from the exact value, and bitwise where every sum is exact.  An empty list gives an empty vector."""
+    A = _list_rows(A, rows)
+    x = np.asarray(x)
+    if np.iscomplexobj(x) or x.shape != (A.shape[1],):
+        raise ValueError("x must be a real d-vector")
+    return A @ x.astype(np.float64)
+
+
+def host_list_combine(A, c, rows=None):
+    """ciao_list_combine in numpy (float64): out[j] = sum_m c[m] A[rows[m], j], a d-vector (rows=None: every row in order; c has one
+    element per list position).  The products are what the device forms (c * (double)a, rounded once); the order of addition is numpy's,
+    so the two agree to (M + 3) 2^-53 sum_m |c_m a_mj| each from the exact value, and bitwise where every sum is exact.  An empty list
+    gives zeros."""
+    A = _list_rows(A, rows)
+    c = np.asarray(c)
+    if np.iscomplexobj(c) or c.shape != (A.shape[0],):
+        raise ValueError("c must be a real vector with one element per list position")
+    return A.T @ c.astype(np.float64)
+
+
 def host_gram_cd(G, u, inv, tau, X, tol, max_sweeps):
     """ciao_gram_cd in numpy (float64) -> (X, R, stat): cyclic coordinate descent with covariance updates on a Gram matrix, the
     SPECIFICATION of the device kernel (csrc/gramcd_kernels.h) and its CPU twin -- the two agree bit for bit.

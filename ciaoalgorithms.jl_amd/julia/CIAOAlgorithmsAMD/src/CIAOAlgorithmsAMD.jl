@@ -556,6 +556,28 @@ function gram_rows(F::PackedF{R}, rows::ROCArray{Int64}; w::Union{Nothing,ROCArr
     return G, uv, cs, bs
 end
 
+# list_dots / list_combine: A[rows] x and A[rows]' c over a LIST of rows at the cost of the rows touched (ciao_list_dots, ciao_list_combine;
+# Python twins: Context.list_dots / list_combine; DESIGN.md section 8.16), bit for bit what the same call without a list gives on the
+# gathered copy.  rows: M Int64 ZERO-BASED row numbers on the device (every entry in 0:N-1 -- the caller checks), or nothing: every row
+# in order.  x: d elements of the rows' type; c: M Float64, one per list position.  Float64 results; neither synchronises.
+function list_dots(F::PackedF{R}, x::ROCArray{R}; rows::Union{Nothing,ROCArray{Int64}} = nothing) where {R}
+    length(x) == F.d || throw(ArgumentError("list_dots needs x of length d"))
+    M = rows === nothing ? Int(F.N) : length(rows)
+    out = ROCArray{Float64}(undef, M)
+    check(ccall((:ciao_list_dots, libciao), Int32, (Ptr{Cvoid}, Ref{CiaoProblem}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+                context().h, Ref(cproblem(F)), dptr(rows), Int64(M), dptr(x), dptr(out)))
+    return out
+end
+
+function list_combine(F::PackedF{R}, c::ROCArray{Float64}; rows::Union{Nothing,ROCArray{Int64}} = nothing) where {R}
+    M = rows === nothing ? Int(F.N) : length(rows)
+    length(c) == M || throw(ArgumentError("list_combine needs one coefficient per list position"))
+    out = ROCArray{Float64}(undef, Int(F.d))
+    check(ccall((:ciao_list_combine, libciao), Int32, (Ptr{Cvoid}, Ref{CiaoProblem}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+                context().h, Ref(cproblem(F)), dptr(rows), Int64(M), dptr(c), dptr(out)))
+    return out
+end
+
 function gram_stats(F::PackedF{R}) where {R}
     (F.loss == LOSS_LS || F.loss == LOSS_LOGISTIC) || throw(ArgumentError("Gram statistics need real LeastSquares or logistic rows"))
     F.N >= 1 || throw(ArgumentError("Gram statistics need at least one row"))

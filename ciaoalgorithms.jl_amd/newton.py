@@ -23,7 +23,8 @@ pass per line-search trial (the accepted trial's dots are the next iteration's);
 
 `rows` is a small protocol (vector, as64, dots, loss, gradient, hessian, certificate, stream) with two implementations: DeviceRows(ctx, F) -- Context.full_gradient, row_dots, margin_stats,
 certificate(samples=True) and gram(weights=) -- and HostRows(A, y) -- numpy and host_route -- so that the driver runs end to end
-without a GPU.  solvers.py imports nothing of this module.
+without a GPU.  Both take rows=, a list of row numbers: the same problem on A[rows], y[rows] -- on the device without a gathered copy,
+through Context.list_dots, list_combine and gram(rows=).  solvers.py imports nothing of this module.
 """
 from __future__ import annotations
 
@@ -46,7 +47,8 @@ HOST_SUBPROBLEM_D = 2048  # up to this d the d x d subproblem is solved on the h
 
 class Passes(NamedTuple):
     gram: int          # weighted Gram passes (N d^2 flops each)
-    first_order: int   # full-gradient, row-dots and certificate passes (N d elements read each)
+    first_order: int   # full-gradient, row-dots and certificate passes (N d elements read each); for DeviceRows(rows=) the list passes
+                       # made (Context.list_dots / list_combine): M d elements each, M / N of a pass over A; and the Gram passes likewise
 
 
 class NewtonResult(NamedTuple):
@@ -67,9 +69,19 @@ def _sigmoid_weights(t):
 
 class DeviceRows:
     """Logistic rows packed for the device: F = device.PackedF.logistic(A, y) on ctx (float32 or float64 rows, d <= 4096); refused on
-    a row-sharded context."""
+    a row-sharded context.
 
-    def __init__(self, ctx, F):
+    rows: None (every row of F: the calls, and the bits, of the full passes), or a contiguous int64 device vector of M >= 1 row numbers
+    in [0, N) -- any order, repeats allowed (a training fold, a bootstrap resample): the logistic problem on A[rows], y[rows] WITHOUT a
+    gathered copy.  Then N = M; dots is Context.list_dots (a float64 M-vector); gradient(x) is
+    Context.list_combine(c) / M with c_m = -y_m sigma(-y_m dots_m) formed in float64 torch on the M-vector, as the weights of hessian
+    are; hessian is Context.gram(weights=, rows=); loss is the four logistic numbers of host_route.host_margin_stats by the same stable
+    evaluation in float64 torch against F.b[rows]; certificate is _certificate from one gradient and one dots pass.  The list is
+    checked against [0, N) once, here.  The row dots of the vector last passed to dots() are kept, so that gradient() and
+    certificate() at that same (unmodified) tensor do not read the rows again; list_passes counts the list passes made
+    (Passes.first_order reports them: each costs M / N of a pass over A)."""
+
+    def __init__(self, ctx, F, rows=None):
         from .device import PackedF
         if not isinstance(F, PackedF) or F.loss != L.LOSS_LOGISTIC:
             raise L.CiaoError(L.ERR_ARG, "DeviceRows takes a device.PackedF of logistic rows (PackedF.logistic)")
@@ -79,6 +91,15 @@ class DeviceRows:
             raise L.CiaoError(L.ERR_ARG, "DeviceRows needs at least one row (N = 0)")
         self.ctx, self.F = ctx, F
         self.N, self.d, self.dtype, self.device = int(F.N), int(F.d), F.dtype, F.A.device
+        self.rows, self.list_passes = None, None
+        if rows is not None:
+            rows, M = ctx._row_list(F, rows, True, "DeviceRows")
+            if M < 1:
+                raise L.CiaoError(L.ERR_ARG, "DeviceRows needs at least one row (an empty list)")
+            self.rows, self.N, self.list_passes = rows, M, 0
+            with self.stream():
+                self.y = F.b[rows].double()
+            self._kept = None   # (x, its version, its row dots)
 
     def stream(self):
         """torch's own operations on these rows' vectors run inside this: on the context's stream, behind the kernels that produced
@@ -100,39 +121,78 @@ class DeviceRows:
             return torch.as_tensor(x).to(device=self.device, dtype=torch.float64)
 
     def dots(self, x):
-        return self.ctx.row_dots(self.F, x)
+        if self.rows is None:
+            return self.ctx.row_dots(self.F, x)
+        kept = self._kept
+        if kept is not None and kept[0] is x and kept[1] == x._version:
+            return kept[2]
+        with self.stream():
+            out = self.ctx.list_dots(self.F, x, rows=self.rows, check_rows=False)
+        self.list_passes += 1
+        self._kept = (x, x._version, out)
+        return out
 
     def loss(self, dots, s=1.0):
-        st = self.ctx.margin_stats(self.F, dots, s)
-        return st.loss_sum / self.N, st.entropy
+        if self.rows is None:
+            st = self.ctx.margin_stats(self.F, dots, s)
+            return st.loss_sum / self.N, st.entropy
+        from .scoring import margin_stats_torch
+        with self.stream():
+            st = margin_stats_torch("logistic", dots, self.y, s)
+        return st[0] / self.N, st[1]
 
     def gradient(self, x):
         import torch
-        with self.stream():                    # (av is allocated on the stream that writes and reads it)
-            av = torch.empty_like(x)
-            self.ctx.full_gradient(self.F, x, av)
-            return av.double()
+        if self.rows is None:
+            with self.stream():                    # (av is allocated on the stream that writes and reads it)
+                av = torch.empty_like(x)
+                self.ctx.full_gradient(self.F, x, av)
+                return av.double()
+        dots = self.dots(x)
+        with self.stream():
+            t = self.y * dots
+            e = torch.exp(-t.abs())
+            p = torch.where(t >= 0, e / (1.0 + e), 1.0 / (1.0 + e))           # sigma(-t)
+            g = self.ctx.list_combine(self.F, -self.y * p, rows=self.rows, check_rows=False)
+            self.list_passes += 1
+            return g / self.N
 
     def hessian(self, dots):
         with self.stream():
-            w = _sigmoid_weights(self.F.b.double() * dots.double())
-            return self.ctx.gram(self.F, u=None, colsum=None, bsum=None, weights=w)[0]
+            if self.rows is None:
+                w = _sigmoid_weights(self.F.b.double() * dots.double())
+                return self.ctx.gram(self.F, u=None, colsum=None, bsum=None, weights=w)[0]
+            w = _sigmoid_weights(self.y * dots)
+            return self.ctx.gram(self.F, u=None, colsum=None, bsum=None, weights=w, rows=self.rows, check_rows=False)[0]
 
     def certificate(self, x, mu, gamma):
-        from .device import ProxG
-        return self.ctx.certificate(self.F, ProxG(L.PROX_L1, lam=mu), x, gamma, samples=True)
+        if self.rows is None:
+            from .device import ProxG
+            return self.ctx.certificate(self.F, ProxG(L.PROX_L1, lam=mu), x, gamma, samples=True)
+        with self.stream():
+            return _certificate(self, self.as64(x), self.gradient(x), self.dots(x), mu, gamma)
 
 
 class HostRows:
     """The same rows on the host: A a real N x d numpy matrix (float32 or float64), y its N labels (+-1).  Row dots and the gradient
-    are formed in A's dtype, as the device forms them; the statistics and the weighted Gram matrix (host_route.host_gram) in double."""
+    are formed in A's dtype, as the device forms them; the statistics and the weighted Gram matrix (host_route.host_gram) in double.
 
-    def __init__(self, A, y):
+    rows: None, or an integer vector of M >= 1 row numbers in [0, N), any order, repeats allowed: the problem on the gathered copies
+    A[rows], y[rows] -- bit for bit HostRows(A[rows], y[rows])."""
+
+    def __init__(self, A, y, rows=None):
         import numpy as np
         import torch
         A, y = np.asarray(A), np.asarray(y)
         if A.ndim != 2 or A.dtype not in (np.float32, np.float64) or y.shape != (A.shape[0],) or A.shape[0] < 1:
             raise ValueError("HostRows: A must be a float32 / float64 N x d matrix with N >= 1 and y an N-vector")
+        if rows is not None:
+            rows = np.asarray(rows.cpu() if hasattr(rows, "cpu") else rows)
+            if rows.ndim != 1 or not np.issubdtype(rows.dtype, np.integer) or rows.size < 1:
+                raise ValueError("HostRows: rows must be an integer vector of at least one row number")
+            if rows.min() < 0 or rows.max() >= A.shape[0]:
+                raise ValueError(f"rows: entries must lie in [0, {A.shape[0]})")
+            A, y = A[rows], y[rows]
         self.A, self.y = A, y.astype(A.dtype)
         self.N, self.d = A.shape
         self.dtype, self.device = (torch.float32 if A.dtype == np.float32 else torch.float64), torch.device("cpu")
@@ -234,6 +294,7 @@ def logistic_newton(rows, mu, x0=None, gap=1e-9, max_outer=30, gamma=1.0, subpro
         x = rows.vector(torch.zeros(rows.d, dtype=torch.float64) if x0 is None else rows.as64(x0))
         eps = float(torch.finfo(rows.dtype).eps)
         n_gram = n_first = outer = 0
+        list_passes0 = getattr(rows, "list_passes", None)
         last = None
         dots = rows.dots(x)
         n_first += 1
@@ -281,6 +342,8 @@ def logistic_newton(rows, mu, x0=None, gap=1e-9, max_outer=30, gamma=1.0, subpro
                 break
         final = rows.certificate(x, mu, gamma)
         n_first += 1
+        if list_passes0 is not None:   # rows over a list count their own passes (a gradient at a new vector is two, at a kept one one)
+            n_first = rows.list_passes - list_passes0
         converged = bool(final.gap <= gap * max(1.0, final.objective))
         if reason == "gap" and not converged:
             # the iteration's own evaluation of the gap (full gradient + margin statistics) met the bound and the certificate's pass over the

@@ -22,12 +22,43 @@ class LogisticScore(NamedTuple):
     min_margin: float         # min_i y_i a_i'x
 
 
-def score(ctx, F, x):
-    """LeastSquaresScore or LogisticScore of x on the rows of F (a device.PackedF of LeastSquares or logistic rows); synchronises."""
+def margin_stats_torch(kind, dots, b, s=1.0):
+    """The four numbers of ciao_margin_stats from float64 torch vectors (dots, and b = the targets / labels, of one length), by the same
+    stable evaluation as host_route.host_margin_stats: the statistics of a row LIST, whose dots are an M-vector (Context.list_dots).
+    The order of addition is torch's.  Synchronises."""
+    import torch
+    dots, b = dots.double(), b.double()
+    if kind == "ls":
+        r = dots - b
+        return float((r * r).sum()), float(b.sum()), float((b * b).sum()), float(r.abs().max())
+    t = b * dots
+    e = torch.exp(-t.abs())
+    big, small = 1.0 / (1.0 + e), e / (1.0 + e)
+    v = s * torch.where(t >= 0, small, big)
+    w = (1.0 - s) + s * torch.where(t >= 0, big, small)
+    xlogx = lambda u: torch.where(u > 0, u * torch.log(torch.where(u > 0, u, torch.ones_like(u))), torch.zeros_like(u))
+    return (float((torch.clamp(-t, min=0.0) + torch.log1p(e)).sum()), float((xlogx(v) + xlogx(w)).sum()), float((t <= 0).sum()), float(t.min()))
+
+
+def score(ctx, F, x, rows=None):
+    """LeastSquaresScore or LogisticScore of x on the rows of F (a device.PackedF of LeastSquares or logistic rows); synchronises.
+
+    rows: a contiguous int64 device vector of M >= 1 row numbers in [0, N), any order, repeats allowed -> the score over A[rows],
+    b[rows] (held-out rows, a fold) at the cost of the rows touched: Context.list_dots, then float64 torch operations on the
+    M-vector."""
     from . import _lib as L
     from .host_route import _score
-    stats = ctx.margin_stats(F, ctx.row_dots(F, x), 1.0)
-    return _score("logistic" if F.loss == L.LOSS_LOGISTIC else "ls", tuple(stats), F.N)
+    kind = "logistic" if F.loss == L.LOSS_LOGISTIC else "ls"
+    if rows is None:
+        stats = ctx.margin_stats(F, ctx.row_dots(F, x), 1.0)
+        return _score(kind, tuple(stats), F.N)
+    from .stepsize import _on_stream
+    with _on_stream(ctx):
+        dots = ctx.list_dots(F, x, rows=rows)
+        if dots.numel() < 1:
+            raise ValueError("score: rows must name at least one row")
+        stats = margin_stats_torch(kind, dots, F.b[rows], 1.0)
+    return _score(kind, stats, int(dots.numel()))
 
 
 def score_many(ctx, F, xs):

@@ -352,6 +352,22 @@ CIAO_API int32_t ciao_gram_weighted(ciao_ctx *ctx, const ciao_problem *p, const 
  * launched.  Workspace: ciao_gram's.  Does not synchronise, except where that workspace has to grow. */
 CIAO_API int32_t ciao_gram_rows(ciao_ctx *ctx, const ciao_problem *p, const int64_t *idx, int64_t M, const double *w, double *G, int64_t ldg,
                                 double *u, double *colsum, double *bsum);
+/* EXTENSION beyond the reference: a matrix-vector product and its adjoint over a LIST of rows, the first-order passes of a problem on a
+ * row subset (a training fold, held-out rows, a bootstrap resample) at the cost of the rows touched.  DESIGN.md section 8.16.
+ *     ciao_list_dots     out[m] = a_{idx[m]}' x                 m = 0 .. M-1   (M device doubles)
+ *     ciao_list_combine  out[j] = sum_m c[m] A[idx[m], j]       j = 0 .. d-1   (d device doubles)
+ * idx: M device int64 row numbers (LOCAL rows on a row-sharded context) at any 8-byte-aligned address, any order, repeats allowed, or
+ * NULL: position = row, and M must equal p->N.  x: d device elements of p->dtype; c: M device DOUBLES, one per list position, at any
+ * 8-byte-aligned address.  Products and sums in double.  Both give BIT FOR BIT what the same call with idx = NULL gives on the gathered
+ * copy A[idx] (c unchanged), for every ld, base and alignment of A, idx, x and c: the order of addition of a row's dot product is a
+ * function of d alone (one row has one bit pattern at every position of every list), that of the combination of (M, d) alone.  A is
+ * read only: the rows named, columns [0, d) of them; nothing beyond idx[M-1] / c[M-1].  An entry outside [0, N) issues no load:
+ * out[m] = 0 in the dots, no term in the combination (Context.list_dots / list_combine refuse such a list before any launch).
+ * Refused with CIAO_ERR_ARG and nothing launched: NULL ctx / p / x / c / out; M < 0; idx = NULL with M != N; idx, c or out not aligned
+ * to 8 bytes; complex problems; CIAO_LOSS_ZERO; d > 4096.  M = 0: nothing is launched (ciao_list_combine sets out to d zeros).
+ * Workspace of ciao_list_combine: ciao_col_sqnorms' partial d-vectors.  Neither synchronises, except where that workspace has to grow. */
+CIAO_API int32_t ciao_list_dots(ciao_ctx *ctx, const ciao_problem *p, const int64_t *idx, int64_t M, const void *x, double *out);
+CIAO_API int32_t ciao_list_combine(ciao_ctx *ctx, const ciao_problem *p, const int64_t *idx, int64_t M, const double *c, double *out);
 /* EXTENSION beyond the reference: cyclic coordinate descent with covariance updates for the lasso on a Gram matrix (glmnet's inner loop),
  * K models in one launch, one workgroup each.  DESIGN.md section 8.14.  Everything is DOUBLE and on the device:
  *     min_x (c/2)(x'G x - 2 u'x + const) + mu_k ||x||_1,   tau[k] = mu_k / c
