@@ -10,7 +10,7 @@ The directory name contains a dot, so it is loaded under the importable alias `c
     sampling.py      injected index streams (the reference's RNG draws are an explicit input here)
     solvers.py       SVRG / SAGA / SAG / Finito constructors, functors, iterator(), solution()
     parallel.py      row sharding + torch.distributed (RCCL) all-reduce hook
-    gram.py          Gram statistics (plain and with a weight per row) and what follows from them in d-space: GramLasso, lasso_path, lasso_cd (coordinate descent: ciao_gram_cd)
+    gram.py          Gram statistics (plain and with a weight per row) and what follows from them in d-space: GramLasso, lasso_path, lasso_cd (coordinate descent: ciao_gram_cd; with bounds, penalty factors, a ridge: ciao_gram_cd_general)
     cv.py            K-fold cross-validation of the lasso path in d-space: the folds' Gram statistics from passes over row lists (ciao_gram_rows)
                      and of the l1-logistic path (logistic_cv): every fold a problem on a row list (ciao_list_dots, ciao_list_combine)
     newton.py        a proximal Newton path for l1-logistic rows on the weighted Gram pass (DeviceRows / HostRows)
@@ -21,8 +21,8 @@ from . import _lib
 from .sampling import FixedStream, IndexStream
 
 __all__ = ["_lib", "IndexStream", "FixedStream"]
-# the coordinate-descent route of the d-space lasso, by name from the package
-_ELSEWHERE = {"lasso_cd": "gram", "host_gram_cd": "host_route"}
+# the coordinate-descent route of the d-space lasso (DESIGN.md sections 8.14 and 8.17), by name from the package
+_ELSEWHERE = {"lasso_cd": "gram", "host_gram_cd": "host_route", "constrained_gaps": "gram", "host_gram_cd_general": "host_route"}
 
 
 def __getattr__(name):

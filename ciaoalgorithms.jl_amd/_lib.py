@@ -98,6 +98,8 @@ SIGNATURES = {
     "ciao_list_dots": (_i32, [_vp, _PP, _vp, _i64, _vp, _vp]),
     "ciao_list_combine": (_i32, [_vp, _PP, _vp, _i64, _vp, _vp]),
     "ciao_gram_cd": (_i32, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _f64, _i32, _vp, _i64, _vp]),
+    "ciao_gram_cd_general": (_i32, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64,
+                                    _vp, _i64, _vp, _i32, _vp, _i64, _vp]),
     "ciao_svrg_init": (_i32, [_vp, _PP, _vp, _vp, _vp, _vp, _vp]),
     "ciao_svrg_inner": (_i32, [_vp, _PP, _GP, _f64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "ciao_svrg_iterate": (_i32, [_vp, _PP, _GP, _f64, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),

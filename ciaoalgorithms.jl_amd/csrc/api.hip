@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "ciao_ctx.h"
+#include "gramcdg_kernels.h"
 #include "launch.h"
 
 namespace ciao {
@@ -1907,6 +1908,60 @@ int32_t ciao_gram_cd(ciao_ctx *ctx, int64_t d, int64_t K, const double *G, int64
     CIAO_REQUIRE(tol >= 0.0, "ciao_gram_cd: tol must be >= 0 (got %g)", tol);
     CIAO_REQUIRE(max_sweeps >= 1 && max_sweeps <= 1024, "ciao_gram_cd takes 1 <= max_sweeps <= 1024 per launch (got %d): relaunch from the returned X", (int)max_sweeps);
     return launch_gram_cd(ctx, d, K, G, ldg, u, inv, tau, X, ldx, tol, max_sweeps, R, ldr, stat);
+}
+
+int32_t ciao_gram_cd_general(ciao_ctx *ctx, int64_t d, int64_t K, const double *G, int64_t ldg, int64_t sg, int64_t nsets, const int32_t *gsel,
+                             const double *u, int64_t ldu, const double *inv, int64_t ldinv, const double *tau, const double *pf, int64_t ldpf,
+                             const double *lo, int64_t ldlo, const double *hi, int64_t ldhi, double *X, int64_t ldx, const double *tol,
+                             int32_t max_sweeps, double *R, int64_t ldr, double *stat)
+{
+    CIAO_REQUIRE(ctx && G && u && inv && tau && X && tol && stat, "ciao_gram_cd_general: the context, G, u, inv, tau, X, tol or stat is NULL");
+    CIAO_ENTER(ctx);
+    CIAO_REQUIRE(d >= 1 && d <= 4096, "ciao_gram_cd_general takes 1 <= d <= 4096 coordinates (got d=%lld: x, r, the diagonal and t live in LDS)", (long long)d);
+    CIAO_REQUIRE(K >= 1 && K <= 4096, "ciao_gram_cd_general takes 1 <= K <= 4096 models in one launch (got K=%lld)", (long long)K);
+    CIAO_REQUIRE(ldg >= d, "ciao_gram_cd_general: the row stride of G, ldg=%lld, is below d=%lld", (long long)ldg, (long long)d);
+    CIAO_REQUIRE(nsets >= 1 && nsets <= 2147483647, "ciao_gram_cd_general needs at least one Gram matrix (got nsets=%lld)", (long long)nsets);
+    CIAO_REQUIRE(nsets == 1 || sg >= (d - 1) * ldg + d, "ciao_gram_cd_general: the set stride sg=%lld is below (d-1) ldg + d = %lld: the Gram matrices overlap",
+                 (long long)sg, (long long)((d - 1) * ldg + d));
+    CIAO_REQUIRE(ldx >= d, "ciao_gram_cd_general: the stride of X, ldx=%lld, is below d=%lld", (long long)ldx, (long long)d);
+    CIAO_REQUIRE(!R || ldr >= d, "ciao_gram_cd_general: the stride of R, ldr=%lld, is below d=%lld", (long long)ldr, (long long)d);
+    CIAO_REQUIRE((ldu == 0 || ldu >= d) && (ldinv == 0 || ldinv >= d), "ciao_gram_cd_general: the strides of u and inv must be 0 (shared) or >= d=%lld (got %lld, %lld)",
+                 (long long)d, (long long)ldu, (long long)ldinv);
+    CIAO_REQUIRE((!pf || ldpf == 0 || ldpf >= d) && (!lo || ldlo == 0 || ldlo >= d) && (!hi || ldhi == 0 || ldhi >= d),
+                 "ciao_gram_cd_general: the strides of pf, lo and hi must be 0 (shared) or >= d=%lld (got %lld, %lld, %lld)", (long long)d, (long long)ldpf,
+                 (long long)ldlo, (long long)ldhi);
+    CIAO_REQUIRE(((reinterpret_cast<uintptr_t>(G) | reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(inv) | reinterpret_cast<uintptr_t>(tau) |
+                   reinterpret_cast<uintptr_t>(pf) | reinterpret_cast<uintptr_t>(lo) | reinterpret_cast<uintptr_t>(hi) | reinterpret_cast<uintptr_t>(tol) |
+                   reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(R) | reinterpret_cast<uintptr_t>(stat)) & 7u) == 0 &&
+                 (reinterpret_cast<uintptr_t>(gsel) & 3u) == 0,
+                 "ciao_gram_cd_general: a buffer is not aligned to 8 bytes (gsel: 4 bytes)");
+    CIAO_REQUIRE(max_sweeps >= 1 && max_sweeps <= 1024, "ciao_gram_cd_general takes 1 <= max_sweeps <= 1024 per launch (got %d): relaunch from the returned X", (int)max_sweeps);
+    GramCdgArgs a{};
+    a.G = G;
+    a.gsel = gsel;
+    a.u = u;
+    a.inv = inv;
+    a.tau = tau;
+    a.pf = pf;
+    a.lo = lo;
+    a.hi = hi;
+    a.tol = tol;
+    a.X = X;
+    a.R = R;
+    a.stat = stat;
+    a.ldg = ldg;
+    a.sg = sg;
+    a.ldu = ldu;
+    a.ldinv = ldinv;
+    a.ldpf = ldpf;
+    a.ldlo = ldlo;
+    a.ldhi = ldhi;
+    a.ldx = ldx;
+    a.ldr = ldr;
+    a.d = (int)d;
+    a.nsets = (int)nsets;
+    a.max_sweeps = max_sweeps;
+    return launch_gram_cd_general(ctx, a, K);
 }
 
 int32_t ciao_screen(ciao_ctx *ctx, int32_t dtype, int64_t d, const void *grad, const double *colsq, double s, double kappa, double mu,

@@ -201,6 +201,10 @@ int32_t launch_listcomb(ciao_ctx *ctx, const ciao_problem *p, const int64_t *idx
 // Defined in gramcd.hip.
 int32_t launch_gram_cd(ciao_ctx *ctx, int64_t d, int64_t K, const double *G, int64_t ldg, const double *u, const double *inv, const double *tau,
                        double *X, int64_t ldx, double tol, int32_t max_sweeps, double *R, int64_t ldr, double *stat);
+// Its general form (gramcdg_kernels.h; ciao_gram_cd_general): per-model Gram matrix, u, inv, penalty factors, bounds and tol; the
+// arguments, already checked, as the kernel's own block.  Defined in gramcdg.hip.
+struct GramCdgArgs;
+int32_t launch_gram_cd_general(ciao_ctx *ctx, const GramCdgArgs &args, int64_t K);
 
 // ProShI agent rows (init or one batch) + finalize + epilogue.  Specialised in rows_f32.hip / rows_f64.hip.
 template <typename T>

@@ -26,7 +26,7 @@ import math
 from typing import NamedTuple
 
 from . import _lib as L
-from .gram import GramStats, _need_ls, add_stats, gram_stats, host_gram_stats, lasso_path, mse
+from .gram import GramStats, _cd_general, _constraints, _need_ls, add_stats, gram_stats, host_gram_stats, lasso_path, mse
 
 
 class CVResult(NamedTuple):
@@ -87,12 +87,19 @@ def choose(mus, mean, stderr):
     return best, one_se
 
 
-def lasso_cv_from_stats(stats_f, mus, gap=1e-6, method="cd", ctx=None) -> CVResult:
+def lasso_cv_from_stats(stats_f, mus, gap=1e-6, method="cd", ctx=None, fused=False, penalty_factor=None, lower=None, upper=None,
+                        ridge=0.0) -> CVResult:
     """Cross-validation from the folds' statistics alone: pure d-space, on whatever device the statistics live (device statistics with
     method="cd" need the Context to launch on, as gram.lasso_cd).  For each fold f: the training statistics are add_stats of the other
     folds in fold order, the K models come from lasso_path(method=) on them with the gap asked for, and the held-out errors from
     mse(stats_f[f], X).  The table itself is formed on the HOST in float64 (a d x d x K product per fold), so that it does not depend on
-    the device the statistics live on."""
+    the device the statistics live on.
+
+    penalty_factor, lower, upper, ridge: gram.lasso_cd's, for every fold and the refit (method="cd").  fused=True (method="cd"; DESIGN.md
+    section 8.17): the folds' training statistics and the all-rows statistics are stacked and all (folds + 1) K models go through ONE
+    driver loop, one Context.gram_cd_general launch per round, each model on its own fold's Gram matrix, u and tol schedule and frozen
+    on its own gap.  A model's bits do not depend on its neighbours in a launch, so where no model runs into the sweep budget the
+    result is bit for bit that of fused=False."""
     import torch
     stats_f = list(stats_f)
     if len(stats_f) < 2:
@@ -108,9 +115,20 @@ def lasso_cv_from_stats(stats_f, mus, gap=1e-6, method="cd", ctx=None) -> CVResu
     nf = len(stats_f)
     table = torch.empty((nf, K), dtype=torch.float64)
     floor = 0.0
+    kw = dict(penalty_factor=penalty_factor, lower=lower, upper=upper, ridge=ridge)
+    fits = None
+    if fused:
+        if method != "cd":
+            raise ValueError("fused=True needs method='cd': the folds share one coordinate-descent launch")
+        s0 = stats_f[0]
+        pf, lo, hi, rdg, general = _constraints(s0.d, s0.G.device, penalty_factor, lower, upper, ridge)
+        groups = [add_stats([s for g, s in enumerate(stats_f) if g != f]) for f in range(nf)] + [add_stats(stats_f)]
+        fits = _cd_general(groups, mus, None, gap, 2000, ctx, None, pf, lo, hi, rdg, general)
     for f in range(nf):
-        train = add_stats([s for g, s in enumerate(stats_f) if g != f])
-        fit = lasso_path(train, mus, gap=gap, method=method, ctx=ctx)
+        if fits is not None:
+            fit = fits[f]
+        else:
+            fit = lasso_path(add_stats([s for g, s in enumerate(stats_f) if g != f]), mus, gap=gap, method=method, ctx=ctx, **kw)
         X = torch.stack([x.double().cpu() for x in fit.x], dim=1)
         v, fl = mse(stats_f[f].to("cpu"), X)
         table[f] = v
@@ -120,19 +138,21 @@ def lasso_cv_from_stats(stats_f, mus, gap=1e-6, method="cd", ctx=None) -> CVResu
     mean = table.mean(0)
     stderr = table.std(0, unbiased=True) / math.sqrt(nf)
     best, one_se = choose(mus, mean.tolist(), stderr.tolist())
-    path = lasso_path(add_stats(stats_f), mus, gap=gap, method=method, ctx=ctx)
+    path = fits[nf] if fits is not None else lasso_path(add_stats(stats_f), mus, gap=gap, method=method, ctx=ctx, **kw)
     return CVResult(mus, table, mean, stderr, best, one_se, path, floor)
 
 
-def lasso_cv(ctx, F, mus, folds=5, seed=0, gap=1e-6, method="cd") -> CVResult:
+def lasso_cv(ctx, F, mus, folds=5, seed=0, gap=1e-6, method="cd", fused=False, penalty_factor=None, lower=None, upper=None, ridge=0.0) -> CVResult:
     """K-fold cross-validation of the lasso path over the rows of F at one pass over A in total: fold_lists(F.N, folds, seed), then
-    fold_stats (one Gram pass per fold over that fold's row list), then lasso_cv_from_stats.  F: a device.PackedF of LeastSquares rows."""
+    fold_stats (one Gram pass per fold over that fold's row list), then lasso_cv_from_stats (fused and the four constraint keywords are
+    its).  F: a device.PackedF of LeastSquares rows."""
     from .device import PackedF
     if not isinstance(F, PackedF) or F.loss != L.LOSS_LS:
         raise L.CiaoError(L.ERR_ARG, "lasso_cv covers device.PackedF problems of LeastSquares rows (logistic cross-validation is not built "
                                      "here: cv.logistic_cv)")
     lists = fold_lists(F.N, folds, seed, device=F.A.device)
-    return lasso_cv_from_stats(fold_stats(ctx, F, lists), mus, gap=gap, method=method, ctx=ctx)
+    return lasso_cv_from_stats(fold_stats(ctx, F, lists), mus, gap=gap, method=method, ctx=ctx, fused=fused, penalty_factor=penalty_factor,
+                               lower=lower, upper=upper, ridge=ridge)
 
 
 class LogisticCVResult(NamedTuple):

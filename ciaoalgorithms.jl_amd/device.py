@@ -772,6 +772,86 @@ class Context:
                                       _ptr(R), ldr, _ptr(stat)))
         return X, R, stat
 
+    def gram_cd_general(self, G, u, inv, tau, X, tol, max_sweeps, gsel=None, pf=None, lo=None, hi=None, R=True, stat=None):
+        """(X, R, stat): gram_cd with bounds lo <= x <= hi, a penalty factor per coordinate, a ridge term and a Gram matrix, u and tol
+        per model, K models in one launch (include/ciao_hip.h: ciao_gram_cd_general; DESIGN.md section 8.17, with the method to the bit
+        and its numpy mirror).  All float64 device tensors.  G: (d, d) or (S, d, d), row-major with any
+        row stride >= d and any set stride that keeps the sets apart; gsel: an int32 K-vector of set numbers, None: set 0; u, inv, pf,
+        lo, hi: (d,) shared by all models or (K, d) with any row stride >= d; inv_kj = 1 / (G_jj + ridge_k) where that is > 0, else 0;
+        pf, lo, hi None: 1, -inf, +inf; tau: a K-vector; tol: a number (broadcast to a device K-vector) or a device K-vector; X, R,
+        stat, max_sweeps: as gram_cd.  stat's state 3: the model could not run (a gsel outside [0, S), a negative or NaN tol or pf,
+        lo > 0, hi < 0, a NaN bound or tau pf) and its rows of X and R are untouched.  Does not synchronise."""
+        dev = f"cuda:{self.device}"
+
+        def fresh(*shape):
+            t = torch.empty(shape, dtype=torch.float64, device=dev)
+            if self.stream is not None:
+                t.record_stream(self.stream)
+            return t
+
+        def f64(t, name, dim):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == self.device and t.dtype == torch.float64 and t.dim() in dim):
+                raise ValueError(f"{name}: need a float64 tensor on {dev} with {' or '.join(str(n) for n in dim)} dimensions")
+
+        def mat(t, name, rows, cols):
+            f64(t, name, (2,))
+            if not (tuple(t.shape) == (rows, cols) and (t.stride(1) == 1 or cols == 1) and (rows == 1 or t.stride(0) >= cols)):
+                raise ValueError(f"{name}: need a row-major float64 matrix of shape ({rows}, {cols}) on {dev}")
+            return int(t.stride(0)) if rows > 1 else cols
+
+        def per_model(t, name):
+            """a (d,) vector shared by all models -> stride 0; a (K, d) matrix -> its row stride"""
+            if t is None:
+                return 0
+            f64(t, name, (1, 2))
+            if t.dim() == 1:
+                if not (t.shape[0] == d and (t.stride(0) == 1 or d == 1)):
+                    raise ValueError(f"{name}: need a contiguous vector of {d} elements, or a ({K}, {d}) matrix")
+                return 0
+            return mat(t, name, K, d)
+
+        if not (isinstance(X, torch.Tensor) and X.dim() == 2):
+            raise ValueError("X: need a (K, d) float64 device matrix")
+        K, d = int(X.shape[0]), int(X.shape[1])
+        ldx = mat(X, "X", K, d)
+        f64(G, "G", (2, 3))
+        if G.dim() == 2:
+            S, sg, ldg = 1, 0, mat(G, "G", d, d)
+        else:
+            S = int(G.shape[0])
+            if S < 1:
+                raise ValueError("G: need at least one Gram matrix")
+            ldg = mat(G[0], "G[s]", d, d)
+            sg = int(G.stride(0)) if S > 1 else 0
+            if S > 1 and sg < (d - 1) * ldg + d:
+                raise ValueError("G: the Gram matrices overlap (the set stride is below (d - 1) ldg + d)")
+        if u is None or inv is None:
+            raise ValueError("u and inv are needed")
+        ldu, ldinv, ldpf, ldlo, ldhi = (per_model(t, n) for t, n in ((u, "u"), (inv, "inv"), (pf, "pf"), (lo, "lo"), (hi, "hi")))
+        self._dvec(tau, "tau", K)
+        if isinstance(tol, torch.Tensor):
+            self._dvec(tol, "tol", K)
+        else:
+            tol = torch.full((K,), float(tol), dtype=torch.float64, device=dev)
+            if self.stream is not None:
+                tol.record_stream(self.stream)
+        if gsel is not None and not (isinstance(gsel, torch.Tensor) and gsel.is_cuda and gsel.device.index == self.device and gsel.dtype == torch.int32
+                                     and gsel.dim() == 1 and gsel.shape[0] == K and gsel.is_contiguous()):
+            raise ValueError(f"gsel: need a contiguous int32 vector of {K} elements on {dev}")
+        if R is True:
+            R = fresh(K, d)
+        elif R is None or R is False:
+            R = None
+        ldr = mat(R, "R", K, d) if R is not None else 0
+        if stat is None:
+            stat = fresh(K, 4)
+        elif not (isinstance(stat, torch.Tensor) and stat.is_cuda and stat.dtype == torch.float64 and tuple(stat.shape) == (K, 4) and stat.is_contiguous()):
+            raise ValueError(f"stat: need a contiguous float64 device matrix of shape ({K}, 4)")
+        L.check(self.lib.ciao_gram_cd_general(self._h, d, K, _ptr(G), ldg, sg, S, _ptr(gsel), _ptr(u), ldu, _ptr(inv), ldinv, _ptr(tau),
+                                              _ptr(pf), ldpf, _ptr(lo), ldlo, _ptr(hi), ldhi, _ptr(X), ldx, _ptr(tol), int(max_sweeps),
+                                              _ptr(R), ldr, _ptr(stat)))
+        return X, R, stat
+
     # -- SVRG ------------------------------------------------------------------------------------------------------------
     def svrg_init(self, p, x0, av, z, z_full, w):
         L.check(self.lib.ciao_svrg_init(self._h, p.ref, self._vec(x0, p, "x0"), self._vec(av, p, "av"), self._vec(z, p, "z"),

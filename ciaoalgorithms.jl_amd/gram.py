@@ -295,7 +295,8 @@ def _path_gaps(q, mu, X):
     return Fv + gv - dual, Fv + gv
 
 
-def lasso_path(stats: GramStats, mus, x0=None, gap=1e-9, maxit=20000, check_every=10, dtype=None, method="fista", ctx=None) -> LassoPath:
+def lasso_path(stats: GramStats, mus, x0=None, gap=1e-9, maxit=20000, check_every=10, dtype=None, method="fista", ctx=None, penalty_factor=None,
+               lower=None, upper=None, ridge=0.0) -> LassoPath:
     """The lasso min_x f(x) + mu_k ||x||_1 for every mu_k of `mus`, in d-space: FISTA with the step 1 / smoothness_exact(stats), all K
     models as one d x K matrix (one d x d x K product per iteration; A is never read).  Model k stops -- its column is frozen -- at the
     first check (every `check_every` iterations) with gap_k <= gap * max(1, objective_k), the gap being the certified duality gap of
@@ -305,12 +306,15 @@ def lasso_path(stats: GramStats, mus, x0=None, gap=1e-9, maxit=20000, check_ever
     LeastSquares statistics only.
 
     method: "fista" (the default: the iteration above) or "cd": lasso_cd(stats, mus, x0, gap, ctx=ctx, dtype=dtype) -- coordinate descent,
-    on the device kernel where stats.G is on the GPU and a Context is given (maxit and check_every belong to FISTA and are not used)."""
+    on the device kernel where stats.G is on the GPU and a Context is given (maxit and check_every belong to FISTA and are not used).
+    penalty_factor, lower, upper, ridge: lasso_cd's, forwarded with method="cd"; FISTA here solves the plain lasso only and refuses them."""
     import torch
     if method == "cd":
-        return lasso_cd(stats, mus, x0=x0, gap=gap, ctx=ctx, dtype=dtype)
+        return lasso_cd(stats, mus, x0=x0, gap=gap, ctx=ctx, dtype=dtype, penalty_factor=penalty_factor, lower=lower, upper=upper, ridge=ridge)
     if method != "fista":
         raise ValueError(f"method must be 'fista' or 'cd' (got {method!r})")
+    if not (penalty_factor is None and lower is None and upper is None and ridge == 0.0):
+        raise ValueError("penalty_factor, lower, upper and ridge need method='cd': the FISTA path solves the plain lasso")
     q = GramLasso(stats)
     s = stats
     mus = [float(m) for m in mus]
@@ -364,7 +368,8 @@ CD_TOL_DROP = 100.0       # ... divided by this for every model that has not met
 CD_MAX_LAUNCH = 1024      # sweeps one launch may make (ciao_gram_cd's bound)
 
 
-def lasso_cd(stats: GramStats, mus, x0=None, gap=1e-9, max_sweeps=2000, ctx=None, dtype=None) -> LassoPath:
+def lasso_cd(stats: GramStats, mus, x0=None, gap=1e-9, max_sweeps=2000, ctx=None, dtype=None, penalty_factor=None, lower=None, upper=None,
+             ridge=0.0) -> LassoPath:
     """lasso_path's problem by cyclic coordinate descent with covariance updates: an update reads one row of G, a
     coordinate that stays at zero reads none.  With stats.G on the GPU and a device.Context `ctx` the sweeps run in ONE kernel launch for
     all models (Context.gram_cd: a workgroup per model); otherwise in numpy (host_route.host_gram_cd).  The two give the same bits.
@@ -374,9 +379,20 @@ def lasso_cd(stats: GramStats, mus, x0=None, gap=1e-9, max_sweeps=2000, ctx=None
     warm, with tol / 100; until all have met the gap or a model has made max_sweeps sweeps.  A model whose launch moved no coordinate
     at all is at a fixed point of the update in floating point and is frozen as it is (converged = False unless its gap is met).
     x0, dtype and the returned LassoPath are lasso_path's; iterations = the sweeps made, summed over the models.  LeastSquares
-    statistics only, weighted ones included."""
+    statistics only, weighted ones included.
+
+    penalty_factor, lower, upper (a number or a d-vector each), ridge: the problem becomes
+        min_x f(x) + sum_j mu_k penalty_factor_j |x_j| + (ridge / 2) ||x||^2     over  lower_j <= x_j <= upper_j
+    (non-negative and box-constrained lasso; adaptive lasso, unpenalised coordinates with factor 0, excluded ones with +inf; elastic
+    net), with lower <= 0 <= upper.  With all four at their defaults nothing changes; otherwise the same driver runs on
+    Context.gram_cd_general / host_route.host_gram_cd_general and stops on constrained_gaps, and the certificates carry that objective
+    and gap (residual: NaN).  A factor of 0 on a coordinate with an infinite bound is refused without a ridge: no duality gap can stop
+    that solve."""
     import numpy as np
     import torch
+    pf, lo, hi, ridge, general = _constraints(stats.d, stats.G.device, penalty_factor, lower, upper, ridge)
+    if general:
+        return _cd_general([stats], mus, x0, gap, max_sweeps, ctx, dtype, pf, lo, hi, ridge, True)[0]
     q = GramLasso(stats)
     s = stats
     mus = [float(m) for m in mus]
@@ -452,3 +468,226 @@ def _host_cd(G, u, inv, tau, X, tol, max_sweeps):
     """host_route.host_gram_cd on CPU torch tensors (G may have any strides)."""
     from .host_route import host_gram_cd
     return host_gram_cd(G.numpy(), u.numpy(), inv.numpy(), tau.numpy(), X.numpy(), tol, max_sweeps)
+
+
+def _constraints(d, dev, penalty_factor, lower, upper, ridge):
+    """(pf, lo, hi, ridge, general): the three per-coordinate vectors as float64 d-vectors on `dev` (None where left at the default) and
+    whether any of the four leaves the plain lasso.  Refuses what ciao_gram_cd_general would answer with state 3."""
+    import torch
+
+    def vec(v, name):
+        if v is None:
+            return None
+        v = torch.as_tensor(v, dtype=torch.float64).to(dev)
+        v = v.expand(d) if v.dim() == 0 else v
+        if tuple(v.shape) != (d,):
+            raise ValueError(f"{name} must be a number or a vector of d = {d} elements")
+        return v.contiguous()
+
+    pf, lo, hi = vec(penalty_factor, "penalty_factor"), vec(lower, "lower"), vec(upper, "upper")
+    ridge = float(ridge)
+    if pf is not None and not bool((pf >= 0).all()):
+        raise ValueError("penalty_factor must be >= 0 everywhere (+inf excludes a coordinate) and not NaN")
+    if lo is not None and not bool((lo <= 0).all()):
+        raise ValueError("lower must be <= 0 everywhere (-inf: no bound) and not NaN: x = 0 has to be feasible")
+    if hi is not None and not bool((hi >= 0).all()):
+        raise ValueError("upper must be >= 0 everywhere (+inf: no bound) and not NaN: x = 0 has to be feasible")
+    if not (ridge >= 0 and math.isfinite(ridge)):
+        raise ValueError("ridge must be >= 0 and finite")
+    return pf, lo, hi, ridge, not (pf is None and lo is None and hi is None and ridge == 0.0)
+
+
+def constrained_gaps(stats: GramStats, X, mus, penalty_factor=None, lower=None, upper=None, ridge=0.0):
+    """(gap_k, objective_k) of the K columns of X (d x K) for the problems
+
+        min_x  F(x) + g(x),   F(x) = (c/2)(x'G x - 2 u'x + sum b^2),  c = lam / N,
+        g(x) = sum_j mu_k pf_j |x_j| + (ridge / 2) x_j^2   over  lower_j <= x_j <= upper_j   (+inf outside)
+
+    by Fenchel duality, all K at once on X's device: with grad = c (G x - u) and v = -s grad,
+
+        dual = F (2 s - s^2) - s x'grad - sum_j g*_j(v_j),      gap = F + g(x) - dual >= objective - optimum,
+        g*_j(v) = v xh - mu_j |xh| - (ridge / 2) xh^2  at  xh = clamp(soft(v, mu_j) / ridge, lower_j, upper_j)        (ridge > 0)
+                                                           xh = upper_j if v > mu_j, lower_j if v < -mu_j, else 0     (ridge = 0)
+
+    s = 1 with a ridge; otherwise the largest s <= 1 with v_j <= mu_j wherever upper_j = +inf and -v_j <= mu_j wherever lower_j = -inf
+    (those terms are then 0: the scaling lasso_path's gap uses, restricted to the sides that are open to infinity).  An unpenalised
+    coordinate with an infinite side and no ridge forces s = 0 and a gap that never closes.  penalty_factor, lower, upper: a number or
+    a d-vector, None: 1, -inf, +inf.  With the defaults this is the gap lasso_path and lasso_cd stop on, up to rounding."""
+    import torch
+    q = GramLasso(stats)
+    s_ = stats
+    X = q._x(X)
+    if X.dim() == 1:
+        X = X[:, None]
+    dev = X.device
+    d, K = X.shape
+    mu = torch.as_tensor(mus, dtype=torch.float64).to(dev).reshape(-1)
+    if mu.shape[0] != K:
+        raise ValueError(f"{mu.shape[0]} l1 weights for {K} columns")
+    pf, lo, hi, nu, _ = _constraints(d, dev, penalty_factor, lower, upper, ridge)
+    pf = torch.ones(d, dtype=torch.float64, device=dev) if pf is None else pf
+    lo = torch.full((d,), -math.inf, dtype=torch.float64, device=dev) if lo is None else lo
+    hi = torch.full((d,), math.inf, dtype=torch.float64, device=dev) if hi is None else hi
+    c = s_.lam / s_.N
+    grad = c * (s_.G @ X - s_.u[:, None])
+    Fv = q.value(X)
+    if not isinstance(Fv, torch.Tensor):
+        Fv = torch.as_tensor([Fv], dtype=torch.float64, device=dev)
+    muj = mu[None, :] * pf[:, None]                                   # d x K; +inf where a coordinate is excluded
+    zero = torch.zeros_like(X)
+    ax = X.abs()
+    gv = torch.where(ax > 0, muj * ax, zero).sum(0) + 0.5 * nu * (X * X).sum(0)
+    outside = ((X > hi[:, None]) | (X < lo[:, None])).any(0)
+    gv = torch.where(outside, torch.full_like(gv, math.inf), gv)
+    LO, HI = lo[:, None].expand(d, K), hi[:, None].expand(d, K)
+    if nu > 0:
+        sc = torch.ones(K, dtype=torch.float64, device=dev)
+        v = -grad
+        xh = torch.minimum(torch.maximum(torch.sign(v) * torch.clamp(v.abs() - muj, min=0.0) / nu, LO), HI)
+    else:
+        # the sides open to infinity bound s: s (-grad_j) <= mu_j where upper_j = +inf, s grad_j <= mu_j where lower_j = -inf
+        inf = torch.full_like(grad, math.inf)
+        need = torch.minimum(torch.where(torch.isinf(HI) & (grad < 0), muj / -grad, inf), torch.where(torch.isinf(LO) & (grad > 0), muj / grad, inf))
+        sc = torch.clamp(need.amin(0), max=1.0)
+        v = -sc[None, :] * grad
+        xh = torch.where((v > muj) & torch.isfinite(HI), HI, torch.where((v < -muj) & torch.isfinite(LO), LO, zero))
+    axh = xh.abs()
+    conj = (v * xh - torch.where(axh > 0, muj * axh, zero) - 0.5 * nu * xh * xh).sum(0)
+    dual = Fv * (2 * sc - sc * sc) - sc * (X * grad).sum(0) - conj
+    return Fv + gv - dual, Fv + gv
+
+
+CD_UNBOUNDED_FREE = ("lasso_cd: penalty_factor is 0 on a coordinate with an infinite bound and there is no ridge: the dual problem has no "
+                     "finite point in general, so no duality gap can stop the solve.  Bound the coordinate (lower= / upper=), add a ridge, "
+                     "or centre the columns and targets (GramStats.standardized) and leave the coordinate out")
+
+
+def _cd_general(groups, mus, x0, gap, max_sweeps, ctx, dtype, pf, lo, hi, ridge, general):
+    """lasso_cd's driver over SEVERAL statistics at once -> one LassoPath per group: the models of every group go through ONE
+    Context.gram_cd_general launch per round (host_route.host_gram_cd_general without a context), model (g, k) on Gram matrix g with
+    group g's u, its inv = 1 / (G_jj + ridge N / lam), its own tol schedule (1e-7 sum b^2 of the group, divided by 100 per round) and
+    frozen on its own gap.  A model's bits do not depend on the others in the launch, so a group's path is what the driver gives the
+    group alone -- up to the sweep budget, which one launch shares.  general: stop on constrained_gaps and certify with it; otherwise
+    (the plain lasso, all constraints None) on lasso_path's gap, with lasso_cd's certificates."""
+    import numpy as np
+    import torch
+    from .host_route import host_gram_cd_general
+    s0 = groups[0]
+    for s in groups:
+        _need_ls(s, "lasso_cd")
+        if s.d != s0.d or s.G.device != s0.G.device:
+            raise ValueError("the statistics must share d and the device")
+    mus = [float(m) for m in mus]
+    K, S, d = len(mus), len(groups), s0.d
+    if K < 1 or any(not (m > 0 and math.isfinite(m)) for m in mus):
+        raise ValueError("lasso_cd needs at least one l1 weight, every one > 0 and finite")
+    if not (gap > 0 and max_sweeps >= 1):
+        raise ValueError("gap must be > 0 and max_sweeps >= 1")
+    if S * K > 4096:
+        raise ValueError(f"{S} x {K} models exceed one launch (4096)")
+    dev = s0.G.device
+    on_device = dev.type == "cuda" and ctx is not None
+    if dev.type == "cuda" and ctx is None:
+        raise L.CiaoError(L.ERR_ARG, "lasso_cd on device statistics needs the Context to launch on (ctx=); stats.to('cpu') runs the numpy twin")
+    if general and ridge == 0.0 and pf is not None:
+        open_side = torch.ones(d, dtype=torch.bool, device=dev)
+        if lo is not None and hi is not None:
+            open_side = torch.isinf(lo) | torch.isinf(hi)
+        if bool(((pf == 0) & open_side).any()):
+            raise ValueError(CD_UNBOUNDED_FREE)
+    if on_device:
+        from .stepsize import _on_stream
+        stream = lambda: _on_stream(ctx)   # noqa: E731
+    else:
+        import contextlib
+        stream = contextlib.nullcontext
+    qs = [GramLasso(s) for s in groups]
+    with stream():
+        mu = torch.tensor(mus, dtype=torch.float64, device=dev)
+        if x0 is None:
+            X = torch.zeros((S * K, d), dtype=torch.float64, device=dev)
+        elif isinstance(x0, (list, tuple)):
+            if len(x0) != K:
+                raise ValueError(f"{len(x0)} starting points for {K} models")
+            X = torch.stack([qs[0]._x(v) for v in x0], dim=0).repeat(S, 1).contiguous()
+        else:
+            X = qs[0]._x(x0)[None, :].repeat(S * K, 1)
+        Gs = torch.stack([s.G for s in groups], dim=0)
+        Us = torch.stack([s.u for s in groups], dim=0)
+        cs = [s.lam / s.N for s in groups]
+        tau = torch.tensor([m / c for c in cs for m in mus], dtype=torch.float64, device=dev)
+        diags = [torch.diagonal(s.G) for s in groups]
+        if general:
+            dens = [dg + ridge / c for dg, c in zip(diags, cs)]
+        else:
+            dens = diags
+        INVs = torch.stack([torch.where(dn > 0, 1.0 / dn, torch.zeros_like(dn)) for dn in dens], dim=0)
+        tols = [CD_FIRST_TOL * float(s.sum_bb) for s in groups]
+        if any(not (t >= 0 and math.isfinite(t)) for t in tols):
+            raise ValueError("sum_bb must be finite and >= 0")
+        used = [0] * (S * K)
+        done = [False] * (S * K)
+        live = list(range(S * K))
+        while live:
+            budget = min(CD_MAX_LAUNCH, max_sweeps - max(used[m] for m in live))
+            if budget < 1:
+                break
+            idx = torch.tensor(live, dtype=torch.long, device=dev)
+            gidx = torch.tensor([m // K for m in live], dtype=torch.long, device=dev)
+            Xl = X.index_select(0, idx).contiguous()
+            tol = torch.tensor([tols[m // K] for m in live], dtype=torch.float64, device=dev)
+            taul = tau.index_select(0, idx).contiguous()
+            Ul, Il = Us.index_select(0, gidx).contiguous(), INVs.index_select(0, gidx).contiguous()
+            if on_device:
+                _, _, st = ctx.gram_cd_general(Gs, Ul, Il, taul, Xl, tol, budget, gsel=gidx.to(torch.int32), pf=pf, lo=lo, hi=hi, R=None)
+                st = st.cpu().numpy()
+            else:
+                npv = lambda t: None if t is None else t.numpy()   # noqa: E731
+                Xn, _, st = host_gram_cd_general(Gs.numpy(), Ul.numpy(), Il.numpy(), taul.numpy(), Xl.numpy(), tol.numpy(), budget,
+                                                 gsel=gidx.numpy(), pf=npv(pf), lo=npv(lo), hi=npv(hi))
+                Xl = torch.from_numpy(Xn)
+            X.index_copy_(0, idx, Xl)
+            met = {}
+            for g in sorted({m // K for m in live}):
+                pos = [p for p, m in enumerate(live) if m // K == g]
+                ks = torch.tensor([live[p] % K for p in pos], dtype=torch.long, device=dev)
+                Xg = Xl.index_select(0, torch.tensor(pos, dtype=torch.long, device=dev)).t()
+                if general:
+                    gp, obj = constrained_gaps(groups[g], Xg, mu.index_select(0, ks), pf, lo, hi, ridge)
+                else:
+                    gp, obj = _path_gaps(qs[g], mu.index_select(0, ks), Xg)
+                for p, ok in zip(pos, (gp <= gap * torch.clamp(obj, min=1.0)).tolist()):
+                    met[p] = ok
+            nxt = []
+            for pos, m in enumerate(live):
+                used[m] += int(st[pos, 0])
+                if met[pos]:
+                    done[m] = True
+                elif st[pos, 3] not in (2, 3) and st[pos, 1] > 0:
+                    nxt.append(m)
+            live = nxt
+            tols = [t / CD_TOL_DROP for t in tols]
+        out = []
+        for g, s in enumerate(groups):
+            out_dtype = dtype or s.dtype or torch.float64
+            xs = [X[g * K + k].to(out_dtype).contiguous() for k in range(K)]
+            if general:
+                Xr = torch.stack([x.double() for x in xs], dim=1)
+                gp, obj = constrained_gaps(s, Xr, mu, pf, lo, hi, ridge)
+                grad = qs[g].gradient(Xr)
+                Fv = qs[g].value(Xr)
+                viol = torch.zeros_like(Xr)
+                if lo is not None:
+                    viol = torch.maximum(viol, lo[:, None] - Xr)
+                if hi is not None:
+                    viol = torch.maximum(viol, Xr - hi[:, None])
+                nan = math.nan
+                # (the prox residual is NormL1's: it has no meaning under bounds, factors or a ridge)
+                certs = [CertificateResult(float(Fv[k]), float(obj[k] - Fv[k]), float(obj[k]), nan, float(grad[:, k].abs().max()),
+                                           float(Xr[:, k] @ grad[:, k]), float(viol[:, k].max()), float(gp[k])) for k in range(K)]
+            else:
+                dmax = float(diags[g].max())
+                gamma = 1.0 / dmax / cs[g] if dmax > 0 else 1.0
+                certs = [qs[g].certificate(x, m, gamma) for x, m in zip(xs, mus)]
+            out.append(LassoPath(xs, certs, int(np.sum(used[g * K:(g + 1) * K])), done[g * K:(g + 1) * K]))
+    return out

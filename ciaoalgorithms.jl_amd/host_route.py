@@ -607,6 +607,110 @@ def host_gram_cd(G, u, inv, tau, X, tol, max_sweeps):
     return X, R, stat
 
 
+def host_gram_cd_general(G, u, inv, tau, X, tol, max_sweeps, gsel=None, pf=None, lo=None, hi=None):
+    """ciao_gram_cd_general in numpy (float64) -> (X, R, stat): host_gram_cd with bounds lo <= x <= hi, a penalty factor per coordinate,
+    a ridge term (through inv alone) and a Gram matrix, u and tol per model; the SPECIFICATION of the device kernel
+    (csrc/gramcdg_kernels.h) -- the two agree bit for bit.  Model k minimises over lo_kj <= x_j <= hi_kj
+        1/2 x'G x - u_k'x + sum_j t_kj |x_j| + (ridge_k / 2) sum_j x_j^2,     G = G[gsel[k]],   t_kj = tau_k pf_kj (one rounded product)
+    G: d x d or S x d x d; gsel: K set numbers (None: set 0); u, inv, pf, lo, hi: d (shared) or K x d; inv_kj = 1 / (G_jj + ridge_k)
+    where that is > 0, else 0; pf, lo, hi None: 1, -inf, +inf; tol: a number or K of them; tau: K; X: K x d warm starts (not modified).
+    update(j) is host_gram_cd's with a = |rho| - t_kj and, after x+ is formed, `if x+ > hi: x+ = hi; if x+ < lo: x+ = lo` (comparisons,
+    so a NaN goes through to state 2).  A model that cannot run -- gsel[k] outside [0, S); tol_k < 0 or NaN; a pf_kj < 0 or NaN; a t_kj
+    NaN; lo_kj > 0, hi_kj < 0 or either NaN -- ends with state 3: stat = (0, 0, 0, 3), its row of X as given, its row of R NaN (the
+    device leaves that row of R unwritten).  With the defaults the results are host_gram_cd's bit for bit."""
+    G = np.asarray(G, np.float64)
+    if G.ndim == 2:
+        G = G[None]
+    tau = np.asarray(tau, np.float64).reshape(-1)
+    X = np.array(X, dtype=np.float64, ndmin=2)
+    K, d = X.shape
+    if G.ndim != 3 or G.shape[1:] != (d, d) or G.shape[0] < 1 or tau.shape != (K,):
+        raise ValueError("host_gram_cd_general: G must be d x d or S x d x d, tau a K-vector and X K x d")
+    S = G.shape[0]
+
+    def vec(v, name, default):
+        if v is None:
+            return np.full((K, d), default)
+        v = np.asarray(v, np.float64)
+        if v.shape == (d,):
+            return np.broadcast_to(v, (K, d))
+        if v.shape != (K, d):
+            raise ValueError(f"host_gram_cd_general: {name} must be a d-vector (shared) or K x d")
+        return v
+
+    if u is None or inv is None:
+        raise ValueError("host_gram_cd_general: u and inv are needed")
+    U, INV = vec(u, "u", 0.0), vec(inv, "inv", 0.0)
+    PF, LO, HI = vec(pf, "pf", 1.0), vec(lo, "lo", -np.inf), vec(hi, "hi", np.inf)
+    tol = np.asarray(tol, np.float64)
+    tol = np.full(K, float(tol)) if tol.ndim == 0 else tol.reshape(-1)
+    sel = np.zeros(K, np.int64) if gsel is None else np.asarray(gsel).astype(np.int64).reshape(-1)
+    if tol.shape != (K,) or sel.shape != (K,) or max_sweeps < 1:
+        raise ValueError("host_gram_cd_general: tol and gsel must have K elements and max_sweeps must be >= 1")
+    R = np.full((K, d), np.nan)
+    stat = np.zeros((K, 4))
+    with np.errstate(all="ignore"):
+        for k in range(K):
+            t = tau[k] * PF[k]
+            if (not 0 <= sel[k] < S or not tol[k] >= 0 or not (PF[k] >= 0).all() or np.isnan(t).any()
+                    or not (LO[k] <= 0).all() or not (HI[k] >= 0).all()):
+                stat[k] = (0, 0, 0, 3)
+                continue
+            Gk = G[sel[k]]
+            diag = np.diagonal(Gk).copy()
+            x, inv_k, lo_k, hi_k, tol_k = X[k], INV[k], LO[k], HI[k], tol[k]
+            r = U[k].copy()
+            for j in np.flatnonzero(x != 0):
+                r -= x[j] * Gk[j]
+            sweeps, nupd, last_full, state, active = 0, 0, 0.0, 0, False
+            while True:
+                if sweeps >= max_sweeps:
+                    state = 0
+                    break
+                sweeps += 1
+                big, support, bad = 0.0, False, False
+                for j in range(d):
+                    xj = x[j]
+                    if active and xj == 0:
+                        continue
+                    rho = r[j] + diag[j] * xj
+                    a = abs(rho) - t[j]
+                    if a <= 0 and xj == 0:
+                        continue                      # x+ = 0 = x_j: nothing moves
+                    xp = 0.0 if a <= 0 else np.copysign(a, rho) * inv_k[j]
+                    if xp > hi_k[j]:
+                        xp = hi_k[j]
+                    if xp < lo_k[j]:
+                        xp = lo_k[j]
+                    delta = xp - xj
+                    if not np.isfinite(delta):
+                        bad = True
+                        break
+                    if delta != 0:
+                        r -= delta * Gk[j]
+                        x[j] = xp
+                        nupd += 1
+                        ch = diag[j] * (delta * delta)
+                        if ch > big:
+                            big = ch
+                        if (xj == 0) != (xp == 0):
+                            support = True
+                if bad:
+                    state = 2
+                    break
+                if not active:
+                    last_full = big
+                    if big <= tol_k and not support:
+                        state = 1
+                        break
+                    active = True
+                elif big <= tol_k:
+                    active = False
+            R[k] = r
+            stat[k] = (sweeps, nupd, last_full, state)
+    return X, R, stat
+
+
 def host_standardize(A, b=None, center=True, scale=True, refine=True):
     """standardize.standardize in numpy on a host matrix -> (A_std, b_std, mean, scale, b_mean).  The moments are
     standardize.host_column_moments' (the same shift, the same refinement rule, the same default: always refined); scale_j = 1 / sqrt(var_j) with the population variance, 1

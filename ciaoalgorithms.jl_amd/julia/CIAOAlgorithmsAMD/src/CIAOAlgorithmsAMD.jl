@@ -605,6 +605,27 @@ function gram_cd(G::ROCArray{Float64}, u::ROCArray{Float64}, inv::ROCArray{Float
     return X, R, stat
 end
 
+# gram_cd_general: gram_cd with bounds, a penalty factor per coordinate, a ridge term and a Gram matrix, u and tol per model
+# (ciao_gram_cd_general; Python twins: device.Context.gram_cd_general, gram.lasso_cd's keywords; DESIGN.md section 8.17).  G: d x d or
+# d x d x S (symmetric matrices); gsel: K Int32 set numbers, 0-based, or nothing (set 0); u, inv, pf, lo, hi: d (shared) or d x K;
+# inv[j,k] = 1 / (G[j,j] + ridge_k) where that is > 0, else 0; pf, lo, hi: nothing for 1, -Inf, +Inf; tau, tol: K; X: d x K.  stat's
+# state 3: the model could not run (see the header) and its columns of X and R are untouched.  Does not synchronise.
+function gram_cd_general(G::ROCArray{Float64}, u::ROCArray{Float64}, inv::ROCArray{Float64}, tau::ROCArray{Float64}, X::ROCArray{Float64},
+                         tol::ROCArray{Float64}; gsel::Union{Nothing,ROCArray{Int32}} = nothing, pf::Union{Nothing,ROCArray{Float64}} = nothing,
+                         lo::Union{Nothing,ROCArray{Float64}} = nothing, hi::Union{Nothing,ROCArray{Float64}} = nothing, max_sweeps::Int = 1024)
+    d, K = size(X, 1), size(X, 2)
+    S = ndims(G) == 3 ? size(G, 3) : 1
+    (size(G, 1) == d && size(G, 2) == d && length(tau) == K && length(tol) == K) || throw(ArgumentError("gram_cd_general: G must be d x d (x S), tau and tol of length K"))
+    ld(v) = v === nothing ? Int64(0) : (length(v) == d ? Int64(0) : (size(v) == (d, K) ? Int64(d) : throw(ArgumentError("gram_cd_general: a vector must have d elements or be d x K"))))
+    nptr(v) = v === nothing ? Ptr{Cvoid}(C_NULL) : dptr(v)
+    R = ROCArray{Float64}(undef, d, K)
+    stat = ROCArray{Float64}(undef, 4, K)
+    check(ccall((:ciao_gram_cd_general, libciao), Int32,
+                (Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}),
+                context().h, Int64(d), Int64(K), dptr(G), Int64(d), Int64(d * d), Int64(S), nptr(gsel), dptr(u), ld(u), dptr(inv), ld(inv), dptr(tau), nptr(pf), ld(pf), nptr(lo), ld(lo), nptr(hi), ld(hi), dptr(X), Int64(d), dptr(tol), Int32(max_sweeps), dptr(R), Int64(d), dptr(stat)))
+    return X, R, stat
+end
+
 # ======================================================================================================================
 # SVRG  (src/algorithms/SVRG/SVRG.jl, SVRG_basic.jl)
 # ======================================================================================================================

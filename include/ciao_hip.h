@@ -389,6 +389,27 @@ CIAO_API int32_t ciao_list_combine(ciao_ctx *ctx, const ciao_problem *p, const i
  * launch's time).  Does not synchronise. */
 CIAO_API int32_t ciao_gram_cd(ciao_ctx *ctx, int64_t d, int64_t K, const double *G, int64_t ldg, const double *u, const double *inv,
                               const double *tau, double *X, int64_t ldx, double tol, int32_t max_sweeps, double *R, int64_t ldr, double *stat);
+/* EXTENSION beyond the reference: ciao_gram_cd with bounds, a penalty factor per coordinate, a ridge term, and a Gram matrix, u and tol
+ * per model (non-negative and box-constrained lasso, adaptive lasso, elastic net, every fold of a cross-validation in ONE launch).
+ * DESIGN.md section 8.17.  Model k minimises over lo_kj <= x_j <= hi_kj
+ *     1/2 x'G x - u_k'x + sum_j t_kj |x_j| + (ridge_k / 2) sum_j x_j^2,   G = G + gsel[k] sg,   t_kj = tau[k] pf_kj (one rounded product)
+ * G: nsets matrices of d x d at row stride ldg, sg elements apart (sg is not looked at with nsets = 1); gsel: K int32 set numbers, or NULL:
+ * set 0 for all; u, inv, pf, lo, hi: model k's d elements start at k times the vector's stride, a stride of 0 shares one vector among all
+ * models; inv_kj = 1 / (G_jj + ridge_k) where that is > 0, else 0 (the ridge enters nowhere else); pf, lo, hi may each be NULL: 1, -inf,
+ * +inf; tau, tol: K; X, R, stat, max_sweeps: as ciao_gram_cd.
+ *     update(j)  ciao_gram_cd's with a = |rho| - t_kj and, after x+ is formed:  if (x+ > hi_kj) x+ = hi_kj;  if (x+ < lo_kj) x+ = lo_kj
+ *                (comparisons: a NaN goes through to state 2); the sweep loop is ciao_gram_cd's with tol[k]
+ *     state 3    the model cannot run and ends at once, its rows of X and R untouched, nothing of G read for it, the other models
+ *                unaffected: gsel[k] outside [0, nsets); tol[k] < 0 or NaN; a pf_kj < 0 or NaN; a t_kj NaN; lo_kj > 0, hi_kj < 0, or
+ *                either NaN
+ * With pf, lo, hi NULL or at their defaults and one set, X, R and stat are ciao_gram_cd's bit for bit; in general they are a function of
+ * the model's own inputs' bits alone (host_route.host_gram_cd_general reproduces them in numpy).  Refused with CIAO_ERR_ARG and nothing
+ * launched: what ciao_gram_cd refuses (tol: NULL); nsets < 1; sg < (d-1) ldg + d with nsets > 1; a stride of u, inv, pf, lo or hi that
+ * is neither 0 nor >= d; a base not aligned to 8 bytes (gsel: 4).  Does not synchronise. */
+CIAO_API int32_t ciao_gram_cd_general(ciao_ctx *ctx, int64_t d, int64_t K, const double *G, int64_t ldg, int64_t sg, int64_t nsets,
+                                      const int32_t *gsel, const double *u, int64_t ldu, const double *inv, int64_t ldinv, const double *tau,
+                                      const double *pf, int64_t ldpf, const double *lo, int64_t ldlo, const double *hi, int64_t ldhi,
+                                      double *X, int64_t ldx, const double *tol, int32_t max_sweeps, double *R, int64_t ldr, double *stat);
 
 /* ---- SVRG / SVRG++  (SVRG/SVRG_basic.jl) -------------------------------------------------------------------- */
 /* Base.iterate(iter), :57-66: av = full gradient at x0; z_full = x0; z = 0; w = x0. */
