@@ -108,7 +108,8 @@ struct ciao_ctx {
     int64_t chain_no_dma = 0;       // testing: route chains through the register-ring kernel instead of the LDS-DMA one
     int64_t chain_no_ws = 0;        // testing: SVRG / SAGA chains on chain_dma_kernel instead of the wave-specialised chain_ws_kernel
     int64_t chain_ws_issuers = 0;   // tuning: issuer waves of chain_ws_kernel, 1 or 2 (0 = automatic)
-    int long_occ[2][8] = {};        // rows_long_kernel: workgroups per CU by (J == 8, mode), asked of the runtime once (0 = not yet)
+    int long_occ[2][2][8] = {};     // rows_long_kernel: workgroups per CU by (fp64, J == 8, mode), asked of the runtime once (0 = not yet);
+                                    // the two types' kernels differ in registers, so they can differ in resident workgroups
     int64_t force_generic = 0;      // testing: route every rows launch through the generic kernel
 
     std::string last_kernel;

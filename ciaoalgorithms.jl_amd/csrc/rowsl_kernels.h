@@ -260,6 +260,10 @@ __global__ void __launch_bounds__(ROWS_BLOCK) rows_long_kernel(RowsArgs<T> a_by_
         }
 #undef CIAO_LONG_ITER
         if (n > 0) {
+            // Every wave reads tot[] and s_fail at the end of the loop's last collect, and no barrier follows those reads.  Without this
+            // one, wave 0 could overwrite both for the last row while another wave still reads the values of the row before.
+            // Once per launch, outside the row loop.
+            __syncthreads();
             const bool okk = last == 0 ? collect_apply(r0, seq) : (last == 1 ? collect_apply(r1, seq) : collect_apply(r2, seq));
             if (!okk) return;
         }

@@ -47,8 +47,9 @@ int32_t long_plan<CIAO_T>(ciao_ctx *ctx, int mode, int64_t d, int64_t nrows, int
     if (!kern || nrows < 1) return CIAO_ERR_UNSUPPORTED;
     const int64_t S = (nchunks + (int64_t)J * ROWS_BLOCK - 1) / ((int64_t)J * ROWS_BLOCK);
     if (S > LONG_SMAX) return CIAO_ERR_UNSUPPORTED;
-    // (asked of the runtime once per kernel and ctx, not on every launch -- every Finito batch on such rows came through here: ADVICE r4)
-    int &occ = ctx->long_occ[J == 8 ? 1 : 0][mode & 7];
+    // (asked of the runtime once per kernel -- type, J and mode -- and ctx, not on every launch -- every Finito batch on such rows came through here: ADVICE r4)
+    static_assert(RM_AFINITO_INIT < 8, "long_occ has eight slots per (type, J): one per rows mode");
+    int &occ = ctx->long_occ[sizeof(T) == 8 ? 1 : 0][J == 8 ? 1 : 0][mode & 7];
     if (occ == 0) {
         int o = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kern, ROWS_BLOCK, 0) != hipSuccess || o < 1) {
