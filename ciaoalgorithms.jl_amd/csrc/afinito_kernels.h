@@ -2,6 +2,7 @@
 // (any length, complex), afinito_dma_kernel (LDS-DMA).  Split out of chain_kernels.h in round 5.
 #pragma once
 
+#include "afinito_args.h"
 #include "chain_common.h"
 #include "chain_reg_kernels.h"
 #include "chain_dma_kernels.h"
@@ -19,30 +20,6 @@ namespace ciao {
 // the backtracking needs a_i'z and ||z - x_i||^2: one 2-value exchange per trial.  All branches are workgroup-uniform
 // because every thread derives them from the same bitwise-identical reduced scalars.
 // ------------------------------------------------------------------------------------------------------------------
-template <typename T>
-struct AFinitoArgs {
-    const T *A;
-    const T *b;
-    int64_t ld, d, N;
-    T lam;
-    int64_t nsteps;
-    const int64_t *idx;
-    T alpha, tol_b, invN, Nf;
-    double Nd;             // N_total as the reference uses it in `0.5 * iter.N * iter.α / γ` (Float64 whatever R, :128)
-    ProxD<T> g;
-    T *table, *meta, *av, *z;
-    T *hg;                // device scalar: hat_gamma (in/out)
-    long long *counters;  // [0] steps completed, [1] backtracking trials (out)
-    int *errflag;
-    // Row-sharded problem (ciao_ctx_set_shards, as ChainArgs): shard k = global rows [sh_row0[k], sh_row0[k+1]) with its data rows,
-    // its rows of the s-table and its per-sample scalars in allocations of their own (possibly another GPU's); idx holds GLOBAL rows.
-    int nshards;
-    const T *shA[CIAO_MAX_SHARDS];
-    const T *shb[CIAO_MAX_SHARDS];
-    T *shT[CIAO_MAX_SHARDS];
-    T *shM[CIAO_MAX_SHARDS];
-    int64_t sh_row0[CIAO_MAX_SHARDS + 1];
-};
 
 // The shard table of an adaptive Finito chain (41 qwords: shA | shb | shT | shM | sh_row0), to LDS and searched there exactly as the
 // chains' (shard_table_to_lds / shard_resolve above, and why).

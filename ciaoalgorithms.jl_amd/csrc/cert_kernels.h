@@ -11,14 +11,13 @@
 // reproducible from run to run, context to context, and between a caller's av and the library's own.
 #pragma once
 
+#include "cert_ws.h"   // CERT_GRID_CAP, CERT_REC
 #include "ciao_common.h"
 
 namespace ciao {
 
 constexpr int CERT_BLOCK = 256;       // threads of both kernels
 constexpr int CERT_SLICE = 1024;      // coordinates of one workgroup's slice up to CERT_GRID_CAP slices; whole multiples of it beyond
-constexpr int CERT_GRID_CAP = 512;    // workgroups (= partial records) at most
-constexpr int CERT_REC = 8;           // doubles per record: S0 S1 S2 M V + padding to 64 bytes
 
 // the slice of a d-vector: a pure function of d
 __host__ __device__ inline int64_t cert_slice(int64_t d)

@@ -4,7 +4,6 @@
 
 namespace ciao {
 
-static_assert(CERT_WS_DOUBLES == 8 + CERT_GRID_CAP * CERT_REC, "launch.h sizes the certificate workspace");
 
 // rec: cert_grid(d) * CERT_REC doubles of workspace; out: the five results (both device memory)
 template <>

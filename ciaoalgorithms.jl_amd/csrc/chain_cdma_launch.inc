@@ -1,6 +1,7 @@
 // chain_cdma_launch.inc -- host dispatch of chain_cdma_kernel (complex chains on the LDS-DMA ring) for one real type (CIAO_T);
 // units of their own (chain_cdma_f32/f64.hip) so that the build spreads over the cores.
 
+#include "chain_dma_kernels.h"
 #include "ciao_ctx.h"
 #include "launch.h"
 

@@ -8,6 +8,7 @@
 
 #include "ciao_ctx.h"
 #include "launch.h"
+#include "chain_kernels.h"
 #include "chain_ws_kernels.h"
 #include "chain_wide_kernels.h"
 

@@ -4,7 +4,6 @@
 
 namespace ciao {
 
-static_assert(SCREEN_WS_DOUBLES == 8 + CERT_GRID_CAP * CERT_REC, "launch.h sizes the screening rule's workspace");
 
 // out[j] = sum_i A[i,j]^2 (device, d doubles).  The partials live in ctx->partial: nslab * d doubles, at most COLSQ_WS_BYTES (or one
 // d-vector where that alone is more).  Slabs, panels and grid come from colsq_plan(N, d); only the KIND of load depends on the layout.

@@ -16,7 +16,7 @@ static int32_t gramcd_go(ciao_ctx *ctx, const GramCdPlan &pl, const GramCdArgs &
     return CIAO_OK;
 }
 
-// K models of d coordinates; the arguments have been checked (api.hip: ciao_gram_cd).  Block, load kind, grid and LDS come from
+// K models of d coordinates; the arguments have been checked (api_analysis.hip: ciao_gram_cd).  Block, load kind, grid and LDS come from
 // gramcd_plan(d, ldg, alignment of G, K).
 int32_t launch_gram_cd(ciao_ctx *ctx, int64_t d, int64_t K, const double *G, int64_t ldg, const double *u, const double *inv, const double *tau,
                        double *X, int64_t ldx, double tol, int32_t max_sweeps, double *R, int64_t ldr, double *stat)

@@ -16,7 +16,7 @@ static int32_t gramcdg_go(ciao_ctx *ctx, const GramCdgPlan &pl, const GramCdgArg
     return CIAO_OK;
 }
 
-// K models of d coordinates over nsets Gram matrices; the arguments have been checked (api.hip: ciao_gram_cd_general).  Block, load kind,
+// K models of d coordinates over nsets Gram matrices; the arguments have been checked (api_analysis.hip: ciao_gram_cd_general).  Block, load kind,
 // grid and LDS come from gramcdg_plan(d, ldg, sg, alignment of G, K); with one set the set stride plays no part.
 int32_t launch_gram_cd_general(ciao_ctx *ctx, const GramCdgArgs &args, int64_t K)
 {

@@ -1,12 +1,23 @@
-// launch.h -- host dispatch entry points shared by api.hip and the per-type instantiation units.
+// launch.h -- host dispatch entry points shared by the API units (api_*.hip) and the per-type instantiation units.  The launchers are
+// declared against the argument types only: a unit includes the kernel header of what it launches itself (its *_launch.inc).
 #pragma once
 
-#include "chain_kernels.h"
+#include "cert_ws.h"
+#include "ciao_common.h"
 #include "ciao_ctx.h"
-#include "proshi_kernels.h"
-#include "rows_kernels.h"
+#include "peer_args.h"
+#include "rows_args.h"
 
 namespace ciao {
+
+template <typename T>
+struct ChainArgs;         // chain_common.h
+template <typename T>
+struct ProshiArgs;        // proshi_args.h
+template <typename T>
+struct ProshiChainArgs;
+template <typename T>
+struct AFinitoArgs;       // afinito_args.h
 
 // the next reduction's view of the peer mailboxes (advances the sequence number: every rank makes the same reductions in the
 // same order)
@@ -34,37 +45,6 @@ inline int32_t allreduce_hook(ciao_ctx *ctx, void *buf, int64_t count, int32_t d
         set_error("all-reduce hook failed with status %d", hs);
         return CIAO_ERR_HOOK;
     }
-    return CIAO_OK;
-}
-
-// An open chain batch (ciao_ctx_chain_batch_begin): the launch of a chain kernel is RECORDED -- kernel, block, LDS, argument block,
-// the byte ranges of its state and which of them it writes -- and made by ciao_ctx_chain_batch_end, one launch per kernel with one
-// workgroup per chain.  Only the chains without a Finito batch structure are taken (SVRG inner cycles, SAGA / SAG steps).
-template <typename T, int ALG>
-inline int32_t chain_batch_record(ciao_ctx *ctx, const void *kern, unsigned block, size_t lds, const ChainArgs<T> &a)
-{
-    constexpr bool svrg = (ALG == CA_SVRG || ALG == CA_SVRGC);
-    if (!(svrg || ALG == CA_SAGA || ALG == CA_FINITO) || a.nshards > 0) {
-        set_error("a chain batch takes SVRG inner cycles, SAGA / SAG steps and small-batch Finito steps of unsharded problems only");
-        return CIAO_ERR_UNSUPPORTED;
-    }
-    ciao_chain_rec r;
-    r.kern = kern;
-    r.block = block;
-    r.lds = lds;
-    r.args.assign(reinterpret_cast<const unsigned char *>(&a), reinterpret_cast<const unsigned char *>(&a) + sizeof a);
-    const size_t vb = (size_t)a.d * sizeof(T);
-    auto range = [&](int k, const void *p, size_t bytes, bool w) {
-        r.lo[k] = static_cast<const unsigned char *>(p);
-        r.hi[k] = p ? r.lo[k] + bytes : r.lo[k];
-        r.wr[k] = w;
-    };
-    range(0, a.av, vb, !svrg);
-    range(1, a.z, vb, true);
-    range(2, a.zf, vb, false);
-    range(3, a.w, vb, svrg);
-    range(4, svrg ? nullptr : a.table, (size_t)a.N * vb, true);
-    ctx->batch.push_back(std::move(r));
     return CIAO_OK;
 }
 
@@ -124,16 +104,13 @@ template <typename T>
 int32_t launch_long(ciao_ctx *ctx, int mode, int J, int S, int C, RowsArgs<T> &a);
 
 // the certificate's reduction over the d coordinates (cert_kernels.h): five doubles into `out`; rec = workspace of CERT_GRID_CAP records.
-// Specialised in cert_f32.hip / cert_f64.hip.
-constexpr int CERT_WS_DOUBLES = 8 + 512 * 8;   // the results' block + CERT_GRID_CAP * CERT_REC (cert_kernels.h asserts the product)
+// Workspace of ciao_certificate: CertWs (cert_ws.h).  Specialised in cert_f32.hip / cert_f64.hip.
 template <typename T>
 int32_t launch_cert(ciao_ctx *ctx, int64_t d, const ciao_prox_desc *g, const void *x, const void *av, double gamma, double *rec, double *out);
 
 // the per-sample reduction over the N row dots and targets (mstat_kernels.h): four doubles into `out`; rec = workspace of CERT_GRID_CAP
 // records.  s: the literal, or (M_dev non-null) formed on the device as M == 0 ? 1 : min(1, mu / M) with M = *M_dev.  Specialised in
-// mstat_f32.hip / mstat_f64.hip.  Workspace of the entry points that use it (ctx->cert): [0..8) the certificate's results, [8..16) these
-// four, then the records (the two reductions use them one after the other), then the pass's own grad f(x).
-constexpr int MSTAT_WS_DOUBLES = 16 + 512 * 8;
+// mstat_f32.hip / mstat_f64.hip.  Workspace of the entry points that use it: MstatWs (cert_ws.h).
 template <typename T>
 int32_t launch_mstat(ciao_ctx *ctx, int loss, int64_t N, const void *dots, const void *b, double s, const double *M_dev, double mu,
                      double *rec, double *out);
@@ -148,9 +125,8 @@ int32_t launch_mscore(ciao_ctx *ctx, const ciao_problem *p, int K, const void *c
 
 // Gap-safe screening (colsq_kernels.h).  launch_colsq: out[j] = sum_i A[i,j]^2 over the N local rows, d device doubles; the partial
 // d-vectors go to ctx->partial (grown here).  launch_screen: keep[k] = !(s |grad_k| + kappa sqrt(colsq_k) < mu) and their count into
-// *cnt (device); rec = workspace of CERT_GRID_CAP records.  Workspace of ciao_screen (ctx->cert): [0] the count, [8..) the records.
+// *cnt (device); rec = workspace of CERT_GRID_CAP records.  Workspace of ciao_screen: ScreenWs (cert_ws.h).
 // Specialised in colsq_f32.hip / colsq_f64.hip.
-constexpr int SCREEN_WS_DOUBLES = 8 + 512 * 8;
 template <typename T>
 int32_t launch_colsq(ciao_ctx *ctx, const ciao_problem *p, double *out);
 template <typename T>
@@ -159,9 +135,7 @@ int32_t launch_screen(ciao_ctx *ctx, int64_t d, const void *grad, const double *
 
 // Row sums of squares and their summary (rowsq_kernels.h).  launch_rowsq: out[i] = sum_j A[i,j]^2 for the N local rows (N device doubles,
 // or NULL), one record per workgroup into rec (ROWSQ_WG_TARGET records at most) and, where res is non-NULL, {max, argmax, min, sum} into
-// res[0..4) (device).  Workspace of ciao_row_sqnorms (ctx->cert): [0..8) the summary, [8..) the records.  Specialised in rowsq_f32.hip /
-// rowsq_f64.hip.
-constexpr int ROWSQ_WS_DOUBLES = 8 + 2048 * 8;
+// res[0..4) (device).  Workspace of ciao_row_sqnorms: RowsqWs (cert_ws.h).  Specialised in rowsq_f32.hip / rowsq_f64.hip.
 template <typename T>
 int32_t launch_rowsq(ciao_ctx *ctx, const ciao_problem *p, double *out, double *rec, double *res);
 

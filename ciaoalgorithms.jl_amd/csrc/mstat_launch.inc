@@ -4,7 +4,6 @@
 
 namespace ciao {
 
-static_assert(MSTAT_WS_DOUBLES == 16 + CERT_GRID_CAP * CERT_REC, "launch.h sizes the per-sample reduction's workspace");
 
 // rec: cert_grid(N) * CERT_REC doubles of workspace; out: the four results (both device memory).  M_dev non-null: s is formed on the
 // device from *M_dev and mu (mu <= 0: s = 1 is passed as the literal instead).

@@ -9,27 +9,9 @@
 
 #include "chain_kernels.h"
 #include "ciao_common.h"
+#include "proshi_args.h"
 
 namespace ciao {
-
-template <typename T>
-struct ProshiArgs {
-    const T *Q, *q;        // N x ld each
-    int64_t ld, d, N;
-    T eta, lo, hi;
-    const T *gam;          // per-agent stepsizes
-    T invN;
-    const T *x;            // INIT: x0 ; STEP: z
-    T *table;              // N x d
-    int64_t nrows;
-    const int64_t *idx;    // STEP: batch members, or nullptr = the contiguous rows row0 .. row0+nrows; INIT: nullptr (all rows)
-    int64_t row0;
-    T *partial;
-    int64_t pstride;
-    T *pextra;
-    int *errflag;
-    int dense;             // Q holds N dense d x d blocks (row k of agent i at Q + (i*d + k)*ld) instead of N diagonals
-};
 
 // grad f_i(x)_k = Q_k x_k + q_k + eta (x_k - clamp(x_k, lo, hi))
 template <typename T>
@@ -288,19 +270,6 @@ __global__ void __launch_bounds__(256) proshi_dense_kernel(ProshiArgs<T> a)
 // (indices and hazard flags staged in LDS per chunk of visits, exactly as the chain kernels do); an agent revisited inside
 // the look-ahead window has its table entry re-read at use (this thread stored it: program order).
 // ------------------------------------------------------------------------------------------------------------------
-template <typename T>
-struct ProshiChainArgs {
-    const T *Q, *q;
-    int64_t ld, d, N;
-    T eta, lo, hi;
-    const T *gam;
-    T invN, hat_gamma;
-    const int64_t *idx;        // visited agents, batch after batch
-    int64_t nvisits, batch;    // every batch has `batch` members
-    ProxD<T> g;
-    T *table, *av, *z;
-    int *errflag;
-};
 
 constexpr int PROSHI_CH = 1008;   // visits staged at a time (a multiple of both look-ahead depths)
 // look-ahead in visits: as deep as the 6-bit vmcnt allows -- (PD - 1) * (3 DW loads + 1 store) <= 63

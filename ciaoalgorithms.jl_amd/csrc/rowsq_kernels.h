@@ -26,6 +26,7 @@
 // and the smallest value: a NaN in any row makes max, min and sum NaN and argmax the first such row.
 #pragma once
 
+#include "cert_ws.h"   // ROWSQ_WG_TARGET, ROWSQ_REC
 #include "ciao_common.h"
 
 namespace ciao {
@@ -33,10 +34,8 @@ namespace ciao {
 constexpr int ROWSQ_BLOCK = 256;                 // threads of both kernels: four waves
 constexpr int ROWSQ_WAVES = ROWSQ_BLOCK / WAVE;
 constexpr int ROWSQ_U = 8;                       // 16-byte chunks in flight per lane = slots of a lane's sum
-constexpr int ROWSQ_WG_TARGET = 2048;            // workgroups (= records) at most: 8 per CU
 constexpr int64_t ROWSQ_SPLIT_CHUNKS = 4096;     // rows beyond this many chunks (64 KiB): the four waves share a row
 constexpr int ROWSQ_MODE_SPLIT = 4;
-constexpr int ROWSQ_REC = 8;                     // doubles per record: max, argmax, min, sum + padding to 64 bytes
 
 struct RowsqPlan {
     int g_log2;            // lanes of a row's group = 1 << g_log2

@@ -4,7 +4,6 @@
 
 namespace ciao {
 
-static_assert(ROWSQ_WS_DOUBLES == 8 + ROWSQ_WG_TARGET * ROWSQ_REC, "launch.h sizes the workspace of ciao_row_sqnorms");
 
 // out[i] = sum_j A[i,j]^2 (device, N doubles, or NULL) and one record per workgroup in rec; res non-NULL: rowsq_final_kernel leaves
 // {max, argmax, min, sum} there.  Groups, mode, rows per workgroup and grid come from rowsq_plan(N, d); only the KIND of load depends

@@ -323,7 +323,7 @@ class RcclComm:
 
     def all_reduce(self, t: torch.Tensor, stream=None):
         """In-place sum of a float32/float64 device tensor on `stream` (a torch stream; None = the current one): the very call
-        libciao_hip.so makes for the d-vector sums (csrc/api.hip rccl_hook); used by bench.py to time the collective alone."""
+        libciao_hip.so makes for the d-vector sums (csrc/api_comm.hip rccl_hook); used by bench.py to time the collective alone."""
         assert t.is_cuda and t.is_contiguous() and t.dtype in (torch.float32, torch.float64)
         s = stream if stream is not None else torch.cuda.current_stream(t.device)
         self._check(self._lib.ncclAllReduce(C.c_void_p(t.data_ptr()), C.c_void_p(t.data_ptr()), t.numel(),

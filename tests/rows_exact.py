@@ -8,7 +8,7 @@ that is dropped, doubled or stale changes the bits.  `Bounds` computes the condi
 (tests/test_rows_exact_host.py) -- a condition, not a tolerance.
 
 The data.  Least squares; A in {-1, 0, 1} dense; x0, z, av and b in {-2 .. 2}; lam in {1, 1/2}; N_total a power of two (PackedF(...,
-N_total=): the entry points of csrc/api.hip accept any N_total >= N on a context with no communicator -- check_problem -- so every N is
+N_total=): the entry points of csrc/api_*.hip accept any N_total >= N on a context with no communicator -- check_problem, api_core.hip -- so every N is
 reachable with 1 / N_total a power of two); gam[i] in {N_total / 4, N_total / 2}; hat_gamma = N_total / 2 passed in (the entry points
 take it as a number; Finito's own 1 / sum(1 / gam) is a power of two only for uniform gam); prox thresholds 1/2.  Every scalar that
 multiplies a sum is then a power of two, so no expected value depends on whether the compiler contracts a multiply-add (the library is
@@ -158,7 +158,7 @@ def grad(P, n, B, x=None):
 
 
 def saga_init(P, n, B):
-    """SAGA_basic.jl:42-47: table_i = grad f_i(x0); av = (1 / N) sum_i table_i; z = prox_{gamma g}((1 - gamma) x0) (api.hip saga_init_t)"""
+    """SAGA_basic.jl:42-47: table_i = grad f_i(x0); av = (1 / N) sum_i table_i; z = prox_{gamma g}((1 - gamma) x0) (api_solvers.hip saga_init_t)"""
     A, b = P.A[:n], P.b[:n]
     s1 = _s1(P, B, B.total("row dots", A * P.x0, 1), b)
     table = (A * s1[:, None]) * P.lam
@@ -192,7 +192,7 @@ def finito_batch(P, rows, B):
 
 
 def lfinito_batch(P, rows, B):
-    """Finito_LFinito.jl:83-98 with one batch (api.hip lfinito_iterate_t): z_full = prox(av); the full pass av = z_full - (hat_gamma / N)
+    """Finito_LFinito.jl:83-98 with one batch (api_finito.hip lfinito_iterate_t): z_full = prox(av); the full pass av = z_full - (hat_gamma / N)
     sum_i grad f_i(z_full); z = prox(av); the batch av += (hat_gamma / N) sum_i (grad f_i(z_full) - grad f_i(z)) + (sum_i hat_gamma /
     gam_i) (z - z_full) -- on the problem with targets b2.  z stays the z the batch worked with (the reference's `solution`)."""
     rows = np.asarray(rows, np.int64)
@@ -367,7 +367,7 @@ class Case:
         CU count; rows_long_kernel takes no sweep_grid and its n are sized from the CU count."""
         if self.kind == "long":
             C = self.long_clusters(dtype, num_cu)
-            return [(4, 0), (C + 1, 0), (2 * C + 2, 0), (5 * C + 1, 0)]        # (batches of up to 3 such rows run as a chain: api.hip)
+            return [(4, 0), (C + 1, 0), (2 * C + 2, 0), (5 * C + 1, 0)]        # (batches of up to 3 such rows run as a chain: api_finito.hip)
         W1, U = (1 if self.kind == "split" else self.wpb(dtype)), self.unit(dtype)
         rows = lambda units: units * U - (U - 1 if U > 1 else 0)           # a last unit of ONE row where units hold several
         out = []

@@ -135,7 +135,7 @@ class State:
         if alg == "svrg":
             ctx.svrg_inner(D.F, D.g, P.gamma, idx, b["av"].view, b["zsum"].view, b["z_full"].view, b["p"].view)
         elif alg == "svrgc":
-            # the init's full pass caches a_i'x0 for z_full = x0; the iterate's inner cycle then runs on them (api.hip svrg_inner_t)
+            # the init's full pass caches a_i'x0 for z_full = x0; the iterate's inner cycle then runs on them (api_solvers.hip svrg_inner_t)
             ctx.svrg_init(D.F, D.x0.view, b["av"].view, b["zsum"].view, b["z_full"].view, b["p"].view)
             ctx.svrg_iterate(D.F, D.g, P.gamma, idx, D.spec.plus, b["av"].view, b["zsum"].view, b["z_full"].view, b["p"].view,
                              reuse_rowdots=reuse_rowdots)
@@ -164,7 +164,7 @@ class State:
 
 
 def last_launch_steps(n, r):
-    """the steps of the call's LAST chain launch: a short last batch runs as a launch of its own (api.hip same_size_run)"""
+    """the steps of the call's LAST chain launch: a short last batch runs as a launch of its own (api_finito.hip same_size_run)"""
     return n if n % r == 0 else n % r
 
 

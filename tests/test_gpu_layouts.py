@@ -426,7 +426,7 @@ def rows_expect():
                  "shift:table": modes(LONG, GEN, GEN, GEN, LONG), "shift:x1": all_modes(GEN),
                  "shift:x2": modes(LONG, LONG, LONG, LONG, GEN)}
     # ... and the same rows in batches of two: beyond 8192 elements a batch of up to three rows runs as a chain on several workgroups
-    # whatever chain_max_batch says (batch_as_chain, csrc/api.hip), and that chain tests no pointer (CHAIN_EXPECT below): only the
+    # whatever chain_max_batch says (batch_as_chain, csrc/api_finito.hip), and that chain tests no pointer (CHAIN_EXPECT below): only the
     # sweeps and inits are the rows kernels'
     # complex rows (plan_rows' first branch): rows_csplit_kernel for 64 .. 4096 whole chunks with A, the stride, x1, x2 (GRAD2) and the
     # table (saga_init, finito_init, the Finito batch) aligned, else rows_cplx_kernel, which also takes every adaptive init.  pad2: a
@@ -521,7 +521,7 @@ def test_rows_complex(ctx, ciao, dtype, n):
 @DTYPES
 def test_rows_any_shape(ctx, ciao, dtype):
     rows_class(ctx, ciao, "generic", dtype, [(300, 257, "logistic", 40)], opts={"force_generic": 1})
-    # (batches of 12, 12, 12, 4: up to three rows of more than 8192 elements would run as a chain, batch_as_chain of csrc/api.hip)
+    # (batches of 12, 12, 12, 4: up to three rows of more than 8192 elements would run as a chain, batch_as_chain of csrc/api_finito.hip)
     rows_class(ctx, ciao, "generic", dtype, [(12, 5001 if dtype == F64 else 9001, "ls", 12)])
 
 

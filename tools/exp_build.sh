@@ -8,9 +8,9 @@ name="$1"; flags="$2"; shift 2 || true
 root="$(cd "$(dirname "$0")/.." && pwd)"
 mkdir -p "$root/build/$name"
 for u in "$@"; do
-  # api.hip bakes the flags into ciao_build_flags(): it is recompiled for every experiment, whatever the list says -- an
+  # api_core.hip bakes the flags into ciao_build_flags(): it is recompiled for every experiment, whatever the list says -- an
   # experiment library must never report the product library's empty flag string
-  [ "$u" = "api" ] && continue
+  [ "$u" = "api_core" ] && continue
   [ -f "$root/ciaoalgorithms.jl_amd/csrc/$u.o" ] && cp -p "$root/ciaoalgorithms.jl_amd/csrc/$u.o" "$root/build/$name/$u.o" && touch "$root/build/$name/$u.o"
 done
 make -s -C "$root/ciaoalgorithms.jl_amd/csrc" -j8 EXP="$name" EXTRA="$flags" >/dev/null 2>&1
