@@ -86,6 +86,7 @@ SIGNATURES = {
     "ciao_row_dots": (_i32, [_vp, _PP, _vp, _vp]),
     "ciao_margin_stats": (_i32, [_vp, _PP, _vp, _f64, C.POINTER(_f64)]),
     "ciao_margin_stats_multi": (_i32, [_vp, _PP, _i32, _vp, C.POINTER(_f64), C.POINTER(_f64)]),
+    "ciao_margin_stats_multi_rows": (_i32, [_vp, _PP, _vp, _i64, _i32, _vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
     "ciao_certificate_samples": (_i32, [_vp, _PP, _GP, _vp, _f64, C.POINTER(_f64)]),
     "ciao_col_sqnorms": (_i32, [_vp, _PP, _vp]),
     "ciao_screen": (_i32, [_vp, _i32, _i64, _vp, _vp, _f64, _f64, _f64, _vp, C.POINTER(_i64)]),

@@ -224,6 +224,33 @@ int32_t ciao_margin_stats_multi(ciao_ctx *ctx, const ciao_problem *p, int32_t K,
     return DISPATCH(p->dtype, margin_stats_multi_t, ctx, p, K, x, s_host, out_host);
 }
 
+int32_t ciao_margin_stats_multi_rows(ciao_ctx *ctx, const ciao_problem *p, const int64_t *idx, int64_t M, int32_t K, const void *const *x,
+                                     const double *offset_host, const double *s_host, double *out_host)
+{
+    CIAO_REQUIRE(ctx && p && x && out_host, "ciao_margin_stats_multi_rows: the context, the problem, the pointer table or out_host is NULL");
+    CIAO_ENTER(ctx);
+    CIAO_TRY(check_problem(ctx, p));
+    CIAO_TRY(check_samples(p, "ciao_margin_stats_multi_rows"));
+    CIAO_REQUIRE(p->N >= 1, "ciao_margin_stats_multi_rows needs at least one sample (N = 0)");
+    CIAO_REQUIRE(M >= 1, "ciao_margin_stats_multi_rows: the list must name at least one row (got M=%lld)", (long long)M);
+    CIAO_REQUIRE(idx || M == p->N, "ciao_margin_stats_multi_rows: without a row list (idx = NULL) M must be the number of rows, N=%lld (got M=%lld)",
+                 (long long)p->N, (long long)M);
+    CIAO_REQUIRE(aligned8(idx), "ciao_margin_stats_multi_rows: the row list idx is not aligned to 8 bytes");
+    CIAO_REQUIRE(K >= 1 && K <= 256, "ciao_margin_stats_multi_rows: K must be in 1..256 (got %d)", K);
+    CIAO_REQUIRE(p->d <= 1024, "ciao_margin_stats_multi_rows takes rows of at most 1024 elements (got d=%lld): score the models one by one "
+                               "(ciao_list_dots)", (long long)p->d);
+    for (int k = 0; k < K; ++k) {
+        CIAO_REQUIRE(x[k], "ciao_margin_stats_multi_rows: x[%d] is NULL", k);
+        CIAO_REQUIRE((reinterpret_cast<uintptr_t>(x[k]) & 15u) == 0, "ciao_margin_stats_multi_rows: x[%d] is not aligned to 16 bytes (no fallback "
+                                                                      "for lists: score that model with ciao_list_dots)", k);
+        CIAO_REQUIRE(!s_host || (s_host[k] >= 0.0 && s_host[k] <= 1.0),
+                     "ciao_margin_stats_multi_rows: the dual scaling s[%d] must lie in [0, 1] (got %g)", k, s_host[k]);
+        CIAO_REQUIRE(!offset_host || (offset_host[k] - offset_host[k] == 0.0), "ciao_margin_stats_multi_rows: the offset of model %d is not finite (got %g)",
+                     k, offset_host[k]);
+    }
+    return DISPATCH(p->dtype, launch_mscore_rows, ctx, p, idx, M, (int)K, x, offset_host, s_host, out_host);
+}
+
 int32_t ciao_certificate_samples(ciao_ctx *ctx, const ciao_problem *p, const ciao_prox_desc *g, const void *x, double gamma,
                                  double *out_host)
 {

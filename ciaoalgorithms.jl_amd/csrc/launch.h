@@ -122,6 +122,12 @@ template <typename T>
 bool mscore_supported(const ciao_ctx *ctx, const ciao_problem *p, int K, const void *const *x);
 template <typename T>
 int32_t launch_mscore(ciao_ctx *ctx, const ciao_problem *p, int K, const void *const *x, const double *s_host, double *out_host);
+// ... over a list of rows (ciao_margin_stats_multi_rows): idx = M >= 1 device int64 row numbers, or NULL (position = row, M = N);
+// off_host = K host doubles added to model k's dots, or NULL; the plan is that of M rows.  d <= 1024, 16-byte aligned iterates (checked
+// by the caller: no fallback).
+template <typename T>
+int32_t launch_mscore_rows(ciao_ctx *ctx, const ciao_problem *p, const int64_t *idx, int64_t M, int K, const void *const *x,
+                           const double *off_host, const double *s_host, double *out_host);
 
 // Gap-safe screening (colsq_kernels.h).  launch_colsq: out[j] = sum_i A[i,j]^2 over the N local rows, d device doubles; the partial
 // d-vectors go to ctx->partial (grown here).  launch_screen: keep[k] = !(s |grad_k| + kappa sqrt(colsq_k) < mu) and their count into

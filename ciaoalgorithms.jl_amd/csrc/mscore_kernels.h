@@ -28,6 +28,22 @@
 // as (0 + 1) + (2 + 3).  A model's sums: thread (w, h) adds the rows row(h, w), 16 + row(h, w), ... of the partition in order; slots,
 // waves, partitions as above.  All of it is a function of (N, d, T) alone: not of K, of the model's place in the list (a column of an
 // MFMA is computed from its own column of B only), of the other iterates, of the device or of any alignment.
+//
+// The row-list instantiations (ciao_margin_stats_multi_rows): mscore_partial_kernel<MscoreRows<T>, SL, LOSS> is the
+// same kernel text over a LIST of rows, a.idx = M int64 row numbers (or NULL: position = row), written the way
+// gram_partial_kernel<Indexed<...>> was.  List position m plays the part of the row number everywhere: a.N = M, the plan is mscore_parts(M) /
+// mscore_part_rows(M), partitions are ranges of positions.  Two addresses change: the tile row of position m is row idx[m] of A, and b is
+// read at idx[m].  Records, mscore_final_kernel and the order of addition are the ones above, so the outputs are the bits of the call
+// without a list on the gathered copy A[idx], b[idx].
+//   A tile's 16 entries live in ONE register pair of the wave: lane l holds the entry of position t0 + (l & 15), or -1 where the position
+// lies beyond the partition or the entry names no row of A.  The lane that loads chunk q takes the entry of tile row q / CPR from a lane
+// that holds it (a scalar read where a wave's 64 chunks lie in one row).  The entries of a tile are requested one whole tile ahead of the
+// row loads that use them -- those of the tile after next when the next tile's row loads are issued -- so the two-halves staging never
+// waits on an index.  Positions are clamped into the partition (nothing beyond idx[M - 1] is read); row offsets are formed in int64.
+//   An entry outside [0, rows) issues no load, its row is zero in the tile and its (row, model) pairs are SKIPPED by the epilogue, as a
+// partial tile's missing rows are; the 16-byte fast path of a tile needs all 16 entries valid.
+//   a.off (K doubles, or NULL): model k's per-sample terms see (double)dot + off[k] -- one double addition, the intercept of a fitted
+// model.  With off = NULL no addition is made at all: the bits of the kernel above, signed zeros included.
 #pragma once
 
 #include <type_traits>
@@ -59,6 +75,20 @@ __host__ __device__ inline int mscore_parts(int64_t N)
 // MFMA steps per wave and slot: the padded row length is 16 SL
 __host__ __device__ inline int mscore_sl(int64_t d) { return d <= 64 ? 4 : d <= 256 ? 16 : d <= 512 ? 32 : 64; }
 
+// the tag of the row-list instantiations, and what a kernel's first template argument says
+template <typename T>
+struct MscoreRows {};
+template <typename TT>
+struct MscoreElem {
+    using type = TT;
+    static constexpr bool rows = false;
+};
+template <typename T>
+struct MscoreElem<MscoreRows<T>> {
+    using type = T;
+    static constexpr bool rows = true;
+};
+
 template <typename T>
 struct MscoreArgs {
     const T *A;
@@ -74,6 +104,13 @@ struct MscoreArgs {
     double *rec;             // [model blocks][P][16][MSCORE_REC]
 };
 
+template <typename T>
+struct MscoreArgs<MscoreRows<T>> : MscoreArgs<T> {   // N = M, the length of the list
+    const int64_t *idx;   // M row numbers, 8-byte aligned, or NULL: position = row
+    int64_t rows;         // the rows A has: an entry outside [0, rows) is a row that does not exist
+    const double *off;    // K offsets, or NULL: none is added
+};
+
 template <typename T, int SL>
 constexpr size_t mscore_lds_bytes()
 {
@@ -81,9 +118,11 @@ constexpr size_t mscore_lds_bytes()
     return (size_t)4 * MSCORE_TILE * (4 * SL + 16 / sizeof(T)) * sizeof(T) + (size_t)2 * 4 * 4 * WAVE * sizeof(T);
 }
 
-template <typename T, int SL, int LOSS>
-__global__ void __launch_bounds__(MSCORE_BLOCK) mscore_partial_kernel(MscoreArgs<T> a)
+template <typename TT, int SL, int LOSS>
+__global__ void __launch_bounds__(MSCORE_BLOCK) mscore_partial_kernel(MscoreArgs<TT> a)
 {
+    using T = typename MscoreElem<TT>::type;
+    constexpr bool ROWS = MscoreElem<TT>::rows;
     using M = MfmaOf<T>;
     using Acc = typename M::acc;
     constexpr int VEC = 16 / (int)sizeof(T);
@@ -134,13 +173,59 @@ __global__ void __launch_bounds__(MSCORE_BLOCK) mscore_partial_kernel(MscoreArgs
         }
     }
     const double s = model < a.K ? a.s[model] : 1.0;
+    // (ROWS) the model's offset; has_off is uniform in the grid
+    double off = 0.0;
+    bool has_off = false;
+    if constexpr (ROWS) {
+        has_off = a.off != nullptr;
+        if (has_off && model < a.K) off = a.off[model];
+    }
+    // (ROWS) the 16 entries of the tile at t0 (t0 < r_hi): lane l holds the row of position t0 + (l & 15), -1 where there is none
+    auto entries = [&](int64_t t0) -> int64_t {
+        int64_t v = -1;
+        if constexpr (ROWS) {
+            const int64_t pos = t0 + r;
+            const int64_t pc = pos < r_hi ? pos : r_hi - 1;
+            const int64_t e = a.idx ? a.idx[pc] : pc;
+            v = (pos < r_hi && (uint64_t)e < (uint64_t)a.rows) ? e : -1;
+        }
+        return v;
+    };
+    auto entry_of = [&](int64_t ent, int row) -> int64_t {   // the entry of tile row `row`, from a lane that holds it
+        return (int64_t)__shfl((long long)ent, row, WAVE);
+    };
 
     // The wave's 16 x DW piece of the tile at t0, staged in registers: chunk q = 64 i + lane is chunk q % CPR of row q / CPR.  It travels in
     // two halves (i below / from NLD / 2: the upper and the lower rows), so that the loads of the tile after next for the first half are in
     // flight while the second half of the next tile is awaited: the memory queue of the CU never runs empty.
     Vld st[NLD];
-    auto load_half = [&](auto half_tag, int64_t t0) {
+    auto load_half = [&](auto half_tag, int64_t t0, int64_t ent) {   // ent (ROWS): entries(t0)
         constexpr int I0 = decltype(half_tag)::value == 0 ? 0 : NLD / 2, I1 = decltype(half_tag)::value == 0 ? NLD / 2 : NLD;
+        if constexpr (ROWS) {
+            const bool whole = a.vec16 && (int64_t)(w + 1) * DW <= a.d && __all(ent >= 0);   // (uniform in the wave)
+#pragma unroll
+            for (int i = I0; i < I1; ++i) {
+                const int q = i * WAVE + lane;
+                int64_t row;
+                if constexpr (CPR >= WAVE) {   // the wave's 64 chunks of one load lie in one row: a scalar read
+                    constexpr int CPW = CPR / WAVE;
+                    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(uint64_t)ent, i / CPW);
+                    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)ent >> 32), i / CPW);
+                    row = (int64_t)(((uint64_t)hi << 32) | lo);
+                } else {
+                    row = entry_of(ent, q / CPR);
+                }
+                const int64_t col = w * DW + (q % CPR) * VEC;
+                const T *src = a.A + row * a.ld + col;   // (not formed into an access where row is -1)
+                if (whole || (a.vec16 && row >= 0 && col + VEC <= a.d)) {
+                    st[i] = __builtin_nontemporal_load(reinterpret_cast<const Vld *>(src));
+                } else {
+#pragma unroll
+                    for (int e = 0; e < VEC; ++e) st[i][e] = (row >= 0 && col + e < a.d) ? __builtin_nontemporal_load(src + e) : T(0);
+                }
+            }
+            return;
+        }
         const bool whole = a.vec16 && t0 + MSCORE_TILE <= r_hi && (int64_t)(w + 1) * DW <= a.d;   // (uniform in the wave)
         if (whole) {
 #pragma unroll
@@ -182,22 +267,44 @@ __global__ void __launch_bounds__(MSCORE_BLOCK) mscore_partial_kernel(MscoreArgs
     T pend = T(0), bpend = T(0), bq = T(0);
     bool pvalid = false;
     int par = 0;
+    // (ROWS) e1, e2: the entries of the next tile and of the tile after next, -1 in every lane where there is no such tile; vq: this
+    // thread's pair of the tile whose label is in bq exists
+    int64_t e1 = -1, e2 = -1;
+    bool vq = false;
 
     if (r_lo < r_hi) {
-        load_half(H0, r_lo);
-        load_half(H1, r_lo);
-        if (r_lo + myrow < r_hi) bq = a.b[r_lo + myrow];
+        const int64_t e0 = entries(r_lo);
+        if constexpr (ROWS) {
+            if (r_lo + MSCORE_TILE < r_hi) e1 = entries(r_lo + MSCORE_TILE);
+            if (r_lo + 2 * MSCORE_TILE < r_hi) e2 = entries(r_lo + 2 * MSCORE_TILE);
+        }
+        load_half(H0, r_lo, e0);
+        load_half(H1, r_lo, e0);
+        if constexpr (ROWS) {
+            const int64_t eb = entry_of(e0, myrow);
+            vq = eb >= 0;
+            if (vq) bq = a.b[eb];
+        } else {
+            if (r_lo + myrow < r_hi) bq = a.b[r_lo + myrow];
+        }
         park_half(H0);
         park_half(H1);
         if (r_lo + MSCORE_TILE < r_hi) {
-            load_half(H0, r_lo + MSCORE_TILE);
-            load_half(H1, r_lo + MSCORE_TILE);
+            load_half(H0, r_lo + MSCORE_TILE, e1);
+            load_half(H1, r_lo + MSCORE_TILE, e1);
         }
     }
     for (int64_t t0 = r_lo; t0 < r_hi; t0 += MSCORE_TILE) {   // (uniform in the workgroup)
         const bool next1 = t0 + MSCORE_TILE < r_hi, next2 = t0 + 2 * MSCORE_TILE < r_hi;
         T bn = T(0);
-        if (t0 + MSCORE_TILE + myrow < r_hi) bn = a.b[t0 + MSCORE_TILE + myrow];
+        bool vn = false;
+        if constexpr (ROWS) {
+            const int64_t eb = entry_of(e1, myrow);
+            vn = eb >= 0;
+            if (vn) bn = a.b[eb];
+        } else {
+            if (t0 + MSCORE_TILE + myrow < r_hi) bn = a.b[t0 + MSCORE_TILE + myrow];
+        }
         // ---- GEMM 1: this wave's share of the 16 x 16 row dots, sixteen bytes per LDS read: lane (row r, slot h), step j: tile[r][h SL + j]
         Acc D = Acc(T(0));
         {
@@ -213,12 +320,21 @@ __global__ void __launch_bounds__(MSCORE_BLOCK) mscore_partial_kernel(MscoreArgs
         // own LDS area, half by half, and each half of the tile after next is requested as soon as its registers are free
         if (next1) {
             park_half(H0);
-            if (next2) load_half(H0, t0 + 2 * MSCORE_TILE);
+            if (next2) load_half(H0, t0 + 2 * MSCORE_TILE, e2);
             park_half(H1);
-            if (next2) load_half(H1, t0 + 2 * MSCORE_TILE);
+            if (next2) load_half(H1, t0 + 2 * MSCORE_TILE, e2);
+        }
+        if constexpr (ROWS) {   // the entries of the tile after the one whose row loads were just issued: first used one iteration from here
+            e1 = e2;
+            e2 = t0 + 3 * MSCORE_TILE < r_hi ? entries(t0 + 3 * MSCORE_TILE) : -1;
         }
         // ---- the tile before: its dot through the per-sample terms, beside the MFMAs above
-        if (pvalid) mstat_elem<T, LOSS>(acc, s, pend, bpend);
+        if (pvalid) {
+            if constexpr (ROWS)
+                mstat_elem_d<LOSS>(acc, s, (double)bpend, has_off ? (double)pend + off : (double)pend);
+            else
+                mstat_elem<T, LOSS>(acc, s, pend, bpend);
+        }
         // ---- the four partial D through LDS; every thread adds the partials of its own pair in wave order
         T *slot = xch + (size_t)par * 4 * 4 * WAVE;
 #pragma unroll
@@ -226,11 +342,17 @@ __global__ void __launch_bounds__(MSCORE_BLOCK) mscore_partial_kernel(MscoreArgs
         __syncthreads();
         pend = (slot[(0 * 4 + w) * WAVE + lane] + slot[(1 * 4 + w) * WAVE + lane]) + (slot[(2 * 4 + w) * WAVE + lane] + slot[(3 * 4 + w) * WAVE + lane]);
         par ^= 1;
-        pvalid = t0 + myrow < r_hi;
+        pvalid = ROWS ? vq : t0 + myrow < r_hi;
         bpend = bq;
         bq = bn;
+        vq = vn;
     }
-    if (pvalid) mstat_elem<T, LOSS>(acc, s, pend, bpend);
+    if (pvalid) {
+        if constexpr (ROWS)
+            mstat_elem_d<LOSS>(acc, s, (double)bpend, has_off ? (double)pend + off : (double)pend);
+        else
+            mstat_elem<T, LOSS>(acc, s, pend, bpend);
+    }
 
     // ---- the workgroup's record: the four slots of a model inside a wave (distances 16, 32: every lane ends with the same bits), then
     // the four waves in wave order through LDS

@@ -24,11 +24,13 @@ __device__ __forceinline__ double mstat_xlogx(double u) { return u > 0.0 ? u * l
 
 // Stable on either side of t = 0: e = exp(-|t|) <= 1, sigma(-t) and sigma(t) are e / (1 + e) and 1 / (1 + e) in the order the sign of t
 // gives.  v = s sigma(-t); w = 1 - v is formed as (1 - s) + s sigma(t), two non-negative terms: no cancellation where v is close to 1.
-template <typename T, int LOSS>
-__device__ __forceinline__ void mstat_elem(MstatAcc &c, double s, T dot, T bi)
+// The double form is what the T-typed one below evaluates after its two conversions; mscore_partial_kernel's row-list instantiations
+// call it with an offset already added to the dot.
+template <int LOSS>
+__device__ __forceinline__ void mstat_elem_d(MstatAcc &c, double s, double bd, double dot)
 {
     if (LOSS == CIAO_LOSS_LOGISTIC) {
-        const double t = (double)bi * (double)dot;
+        const double t = bd * dot;
         const double e = exp(-fabs(t));
         const double big = 1.0 / (1.0 + e), small = e / (1.0 + e);
         const double sneg = t >= 0.0 ? small : big, spos = t >= 0.0 ? big : small;
@@ -38,12 +40,17 @@ __device__ __forceinline__ void mstat_elem(MstatAcc &c, double s, T dot, T bi)
         c.a2 += t <= 0.0 ? 1.0 : 0.0;
         c.m = fmax2(c.m, -t);
     } else {
-        const double b = (double)bi, r = (double)dot - b;
+        const double b = bd, r = dot - b;
         c.a0 += r * r;
         c.a1 += b;
         c.a2 += b * b;
         c.m = fmax2(c.m, fabs(r));
     }
+}
+template <typename T, int LOSS>
+__device__ __forceinline__ void mstat_elem(MstatAcc &c, double s, T dot, T bi)
+{
+    mstat_elem_d<LOSS>(c, s, (double)bi, (double)dot);
 }
 
 // the four waves' values -> one, in wave order, through LDS; valid in thread 0

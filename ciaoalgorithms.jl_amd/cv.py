@@ -165,9 +165,11 @@ class LogisticCVResult(NamedTuple):
     one_se: int         # the index of the largest mu whose mean is <= mean[best] + stderr[best]
     path: list          # K newton.NewtonResult: the refit on all rows, for every mu
     converged: object   # (folds, K) bool: the fold solve ended converged
+    intercepts: list = None   # logistic_cv(intercept=True): the refit's K intercepts (zeros without one)
 
 
-def logistic_cv(ctx, F, mus, folds=5, seed=0, gap=1e-6, subproblem="cd", max_outer=30) -> LogisticCVResult:
+def logistic_cv(ctx, F, mus, folds=5, seed=0, gap=1e-6, subproblem="cd", max_outer=30, intercept=False, intercept_bound=32.0,
+                score_together=False) -> LogisticCVResult:
     """K-fold cross-validation of the l1-logistic path without copying rows: fold_lists(F.N, folds, seed); for
     fold f the training list is the other folds' lists concatenated in fold order and sorted, the K models come from
     newton.logistic_path(DeviceRows(ctx, F, rows=train), mus, ...) -- in the order given, each solve warm-started from the last -- and
@@ -176,11 +178,18 @@ def logistic_cv(ctx, F, mus, folds=5, seed=0, gap=1e-6, subproblem="cd", max_out
     only the rows its list names (M / N of a pass over A each); the columns are not standardised inside the folds.
 
     F: a device.PackedF of logistic rows.  With ctx=None and F = (A, y) numpy arrays the same driver runs on the host: newton.HostRows
-    on gathered copies, the scores from host_route.host_margin_stats."""
+    on gathered copies, the scores from host_route.host_margin_stats.
+
+    intercept, intercept_bound: every fit, the refit included, carries an unpenalised intercept
+    (newton.logistic_newton's keywords) and every score is that of a_i'x + c; the result's intercepts are the refit's.
+    score_together=True: the K models of a fold are scored by ONE scoring.score_many(rows=lists[f], intercepts=) call -- one pass over
+    the held-out rows (ciao_margin_stats_multi_rows) instead of K; the scores agree with the default's to rounding (another order of
+    addition).  The host route takes the same keywords (host_route.host_margin_stats_multi(rows=, offsets=))."""
     import torch
-    from .host_route import _score, host_margin_stats
+    from .host_route import _score, host_margin_stats, host_margin_stats_multi
     from .newton import DeviceRows, HostRows, logistic_path
     host = ctx is None
+    ikw = dict(intercept=True, intercept_bound=intercept_bound) if intercept else {}
     if host:
         import numpy as np
         if not (isinstance(F, (tuple, list)) and len(F) == 2):
@@ -204,18 +213,33 @@ def logistic_cv(ctx, F, mus, folds=5, seed=0, gap=1e-6, subproblem="cd", max_out
     for f in range(nf):
         train = torch.sort(torch.cat([r for g, r in enumerate(lists) if g != f])).values.contiguous()
         rows = HostRows(A, y, rows=train.numpy()) if host else DeviceRows(ctx, F, rows=train)
-        fit = logistic_path(rows, mus, gap=gap, max_outer=max_outer, subproblem=subproblem)
-        for k, r in enumerate(fit):
+        fit = logistic_path(rows, mus, gap=gap, max_outer=max_outer, subproblem=subproblem, **ikw)
+        together = None
+        if score_together:
+            cs = [r.intercept for r in fit] if intercept else None
             if host:
                 held = lists[f].numpy()
+                st = host_margin_stats_multi("logistic", A, [np.asarray(r.x, dtype=np.float64) for r in fit], y, rows=held, offsets=cs)
+                together = [_score("logistic", s4, len(held)) for s4 in st]
+            else:
+                from .scoring import score_many
+                together = score_many(ctx, F, [r.x for r in fit], rows=lists[f], intercepts=cs)
+        for k, r in enumerate(fit):
+            if together is not None:
+                sc = together[k]
+            elif host:
+                held = lists[f].numpy()
                 x = np.asarray(r.x, dtype=np.float64)
-                sc = _score("logistic", host_margin_stats("logistic", A[held].astype(np.float64) @ x, y[held], 1.0), len(held))
+                dots = A[held].astype(np.float64) @ x
+                if intercept:
+                    dots = dots + r.intercept
+                sc = _score("logistic", host_margin_stats("logistic", dots, y[held], 1.0), len(held))
             else:
                 from .scoring import score
-                sc = score(ctx, F, r.x, rows=lists[f])
+                sc = score(ctx, F, r.x, rows=lists[f], intercept=r.intercept)
             loss[f, k], acc[f, k], conv[f, k] = sc.log_loss, sc.accuracy, bool(r.converged)
     mean = loss.mean(0)
     stderr = loss.std(0, unbiased=True) / math.sqrt(nf)
     best, one_se = choose(mus, mean.tolist(), stderr.tolist())
-    path = logistic_path(HostRows(A, y) if host else DeviceRows(ctx, F), mus, gap=gap, max_outer=max_outer, subproblem=subproblem)
-    return LogisticCVResult(mus, loss, acc, mean, stderr, best, one_se, path, conv)
+    path = logistic_path(HostRows(A, y) if host else DeviceRows(ctx, F), mus, gap=gap, max_outer=max_outer, subproblem=subproblem, **ikw)
+    return LogisticCVResult(mus, loss, acc, mean, stderr, best, one_se, path, conv, [r.intercept for r in path])

@@ -466,10 +466,19 @@ class Context:
         L.check(self.lib.ciao_margin_stats(self._h, F.ref, self._vec(dots, F, "dots", F.N), float(s), out))
         return (LogisticStats if F.loss == L.LOSS_LOGISTIC else LeastSquaresStats)(*out)
 
-    def margin_stats_multi(self, F, xs, s=None):
+    def margin_stats_multi(self, F, xs, s=None, rows=None, offsets=None, check_rows=True):
         """margin_stats of the row dots a_i'x_k for K iterates in ONE pass over A, without the N x K dots (include/ciao_hip.h:
         ciao_margin_stats_multi) -> a list of K LogisticStats or LeastSquaresStats.  xs: a list of 1..256 device d-vectors; s: None
-        (= 1 for every model), one number, or K numbers in [0, 1].  Synchronises."""
+        (= 1 for every model), one number, or K numbers in [0, 1].  Synchronises.
+
+        rows: a contiguous int64 device vector of M >= 1 local row numbers, any order, repeats allowed -> the statistics over A[rows],
+        b[rows] at the cost of the rows touched (include/ciao_hip.h: ciao_margin_stats_multi_rows), BIT FOR BIT
+        what the call without a list gives on that gathered copy.  offsets: K finite numbers, model k's statistics are those of the dots
+        a_i'x_k + offsets[k] (one float64 addition: a fitted intercept); None adds nothing.  check_rows: as Context.gram(rows=); with
+        False an entry outside [0, N) is skipped (its sample is not counted).  With rows and offsets both None the call, and its bits,
+        are the ones above.  Where the one-pass kernel does not take the problem (d in 1025..4096, or an iterate that is not 16-byte
+        aligned) every model is scored on its own: list_dots, the offset added in float64, scoring.margin_stats_torch -- with
+        check_rows=False over the entries that name a row, so that both routes skip the others."""
         if isinstance(F, PackedSepQuad):
             raise L.CiaoError(L.ERR_ARG, "margin statistics exist for LeastSquares / logistic rows, not for the sharing problem")
         xs = list(xs)
@@ -482,8 +491,41 @@ class Context:
                 raise L.CiaoError(L.ERR_ARG, f"margin_stats_multi: {len(vals)} scalings for {K} iterates")
             sv = (C.c_double * max(K, 1))(*vals)
         out = (C.c_double * (4 * max(K, 1)))()
-        L.check(self.lib.ciao_margin_stats_multi(self._h, F.ref, K, self._ptr_table(xs, F, "x"), sv, out))
         kind = LogisticStats if F.loss == L.LOSS_LOGISTIC else LeastSquaresStats
+        if rows is None and offsets is None:
+            L.check(self.lib.ciao_margin_stats_multi(self._h, F.ref, K, self._ptr_table(xs, F, "x"), sv, out))
+            return [kind(*out[4 * k:4 * k + 4]) for k in range(K)]
+        rows, M = self._row_list(F, rows, check_rows, "margin_stats_multi")
+        if M < 1:
+            raise L.CiaoError(L.ERR_ARG, "margin_stats_multi: rows must name at least one row")
+        ov = None
+        if offsets is not None:
+            ov = [float(v) for v in offsets]
+            if len(ov) != K:
+                raise L.CiaoError(L.ERR_ARG, f"margin_stats_multi: {len(ov)} offsets for {K} iterates")
+            if any(v - v != 0.0 for v in ov):
+                raise L.CiaoError(L.ERR_ARG, "margin_stats_multi: every offset must be finite")
+        table = self._ptr_table(xs, F, "x")
+        if F.d > 1024 or any(x.data_ptr() % 16 for x in xs):
+            from .scoring import margin_stats_torch
+            from .stepsize import _on_stream
+            if not 1 <= K <= 256:
+                raise L.CiaoError(L.ERR_ARG, f"margin_stats_multi: K must be in 1..256 (got {K})")
+            name, res = ("logistic" if F.loss == L.LOSS_LOGISTIC else "ls"), []
+            with _on_stream(self):
+                if rows is not None and not check_rows:   # the kernel skips an entry that names no row: so does this route
+                    rows = rows[(rows >= 0) & (rows < F.N)].contiguous()
+                    if rows.numel() == 0:                  # the statistics of no sample, as the kernel leaves them
+                        return [kind(0.0, 0.0, 0.0, float("inf") if F.loss == L.LOSS_LOGISTIC else 0.0) for _ in xs]
+                b = F.b if rows is None else F.b[rows]
+                for k, x in enumerate(xs):
+                    dots = self.list_dots(F, x, rows=rows, check_rows=False)
+                    if ov is not None and ov[k] != 0.0:   # (as scoring.score: a zero intercept adds nothing, not even +0.0)
+                        dots = dots + ov[k]
+                    res.append(kind(*margin_stats_torch(name, dots, b, 1.0 if sv is None else sv[k])))
+            return res
+        op = None if ov is None else (C.c_double * max(K, 1))(*ov)
+        L.check(self.lib.ciao_margin_stats_multi_rows(self._h, F.ref, None if rows is None else _ptr(rows), M, K, table, op, sv, out))
         return [kind(*out[4 * k:4 * k + 4]) for k in range(K)]
 
     # -- gap-safe screening (screening.py) ----------------------------------------------------------

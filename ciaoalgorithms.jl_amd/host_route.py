@@ -362,10 +362,29 @@ def host_margin_stats(kind, dots, b, s=1.0):
     return (float(np.sum(np.maximum(-t, 0.0) + np.log1p(e))), float(np.sum(xlogx(v) + xlogx(w))), float(np.sum(t <= 0)), float(np.min(t)))
 
 
-def host_margin_stats_multi(kind, A, xs, b, s=None):
-    """ciao_margin_stats_multi in numpy (float64): K calls of host_margin_stats on the row dots A @ x_k, at s_k (None: 1)."""
-    A = np.asarray(A, np.float64)
-    return [host_margin_stats(kind, A @ np.asarray(x, np.float64).reshape(-1), b, 1.0 if s is None else float(s[k])) for k, x in enumerate(xs)]
+def host_margin_stats_multi(kind, A, xs, b, s=None, rows=None, offsets=None):
+    """ciao_margin_stats_multi in numpy (float64): K calls of host_margin_stats on the row dots A @ x_k, at s_k (None: 1).
+
+    rows, offsets (ciao_margin_stats_multi_rows): gather, then add -- the statistics of A[rows], b[rows] for the dots
+    A[rows] @ x_k + offsets[k]; rows: integer row numbers in [0, N), any order, repeats allowed; offsets: K numbers (None: nothing is
+    added)."""
+    A, b = np.asarray(A, np.float64), np.asarray(b, np.float64)
+    if rows is not None:
+        rows = np.asarray(rows)
+        if rows.ndim != 1 or not np.issubdtype(rows.dtype, np.integer) or rows.size < 1:
+            raise ValueError("host_margin_stats_multi: rows must be an integer vector of at least one row number")
+        if rows.min() < 0 or rows.max() >= A.shape[0]:
+            raise ValueError(f"rows: entries must lie in [0, {A.shape[0]})")
+        A, b = A[rows], b[rows]
+    if offsets is not None and len(offsets) != len(xs):
+        raise ValueError(f"host_margin_stats_multi: {len(offsets)} offsets for {len(xs)} iterates")
+    out = []
+    for k, x in enumerate(xs):
+        dots = A @ np.asarray(x, np.float64).reshape(-1)
+        if offsets is not None:
+            dots = dots + float(offsets[k])
+        out.append(host_margin_stats(kind, dots, b, 1.0 if s is None else float(s[k])))
+    return out
 
 
 def _score(kind, stats, n):

@@ -363,6 +363,27 @@ function margin_stats_multi(F::PackedF{R}, xs::Vector{<:ROCArray{R}}; s::Maybe{V
     return out[:, 1:K]
 end
 
+# ... over a LIST of rows, with an offset (intercept) per model: held-out rows scored for K fitted models in one pass over the rows named
+# (include/ciao_hip.h: ciao_margin_stats_multi_rows; Python twin: Context.margin_stats_multi(rows=, offsets=); DESIGN.md section 8.18).
+# rows: M ≥ 1 Int64 ZERO-BASED row numbers on the device, or nothing: every row in order.  offsets: one Float64 per model, or nothing.
+# d ≤ 1024 and 16-byte aligned iterates: the entry point has no fallback.
+function margin_stats_multi_rows(F::PackedF{R}, xs::Vector{<:ROCArray{R}}; rows::Union{Nothing,ROCArray{Int64}} = nothing,
+                                 offsets::Maybe{Vector{Float64}} = nothing, s::Maybe{Vector{Float64}} = nothing) where {R}
+    K = length(xs)
+    s === nothing || length(s) == K || throw(ArgumentError("as many scalings as iterates"))
+    offsets === nothing || length(offsets) == K || throw(ArgumentError("as many offsets as iterates"))
+    M = rows === nothing ? Int(F.N) : length(rows)
+    xt = Ptr{Cvoid}[dptr(x) for x in xs]
+    out = zeros(Float64, 4, max(K, 1))
+    sp = s === nothing ? Ptr{Float64}(C_NULL) : pointer(s)
+    op = offsets === nothing ? Ptr{Float64}(C_NULL) : pointer(offsets)
+    p = Ref(cproblem(F))
+    GC.@preserve xt s offsets check(ccall((:ciao_margin_stats_multi_rows, libciao), Int32,
+                                          (Ptr{Cvoid}, Ref{CiaoProblem}, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                                          context().h, p, dptr(rows), Int64(M), Int32(K), pointer(xt), op, sp, out))
+    return out[:, 1:K]
+end
+
 # The scores of K fitted models on the rows of F (the training rows, or new rows with the same d) from one pass (scoring.score_many):
 # LeastSquares rows (mse, r2, max_abs_residual), logistic rows (log_loss, accuracy, min_margin), as named tuples.
 function score_many(F::PackedF{R}, xs::Vector{<:ROCArray{R}}) where {R}

@@ -40,16 +40,22 @@ def margin_stats_torch(kind, dots, b, s=1.0):
     return (float((torch.clamp(-t, min=0.0) + torch.log1p(e)).sum()), float((xlogx(v) + xlogx(w)).sum()), float((t <= 0).sum()), float(t.min()))
 
 
-def score(ctx, F, x, rows=None):
+def score(ctx, F, x, rows=None, intercept=0.0):
     """LeastSquaresScore or LogisticScore of x on the rows of F (a device.PackedF of LeastSquares or logistic rows); synchronises.
 
     rows: a contiguous int64 device vector of M >= 1 row numbers in [0, N), any order, repeats allowed -> the score over A[rows],
     b[rows] (held-out rows, a fold) at the cost of the rows touched: Context.list_dots, then float64 torch operations on the
-    M-vector."""
+    M-vector.
+
+    intercept: a finite number c -> the score of the predictions a_i'x + c (newton.logistic_newton(intercept=True); DESIGN.md section
+    8.18): the list route (rows=None: every row), c added to the float64 dots.  0.0 adds nothing and keeps the calls above."""
     from . import _lib as L
     from .host_route import _score
     kind = "logistic" if F.loss == L.LOSS_LOGISTIC else "ls"
-    if rows is None:
+    intercept = float(intercept)
+    if intercept - intercept != 0.0:
+        raise ValueError("score: the intercept must be finite")
+    if rows is None and intercept == 0.0:
         stats = ctx.margin_stats(F, ctx.row_dots(F, x), 1.0)
         return _score(kind, tuple(stats), F.N)
     from .stepsize import _on_stream
@@ -57,18 +63,24 @@ def score(ctx, F, x, rows=None):
         dots = ctx.list_dots(F, x, rows=rows)
         if dots.numel() < 1:
             raise ValueError("score: rows must name at least one row")
-        stats = margin_stats_torch(kind, dots, F.b[rows], 1.0)
+        if intercept != 0.0:
+            dots = dots + intercept
+        stats = margin_stats_torch(kind, dots, F.b if rows is None else F.b[rows], 1.0)
     return _score(kind, stats, int(dots.numel()))
 
 
-def score_many(ctx, F, xs):
+def score_many(ctx, F, xs, rows=None, intercepts=None):
     """[score(ctx, F, x) for x in xs] from ONE pass over the rows of F (Context.margin_stats_multi: up to 256 models a call; the
     N x K predictions never exist): the scores of a regularisation path, of folds or of restarts on held-out rows.  Each agrees with
-    its own score() to rounding (another order of addition).  Synchronises."""
+    its own score() to rounding (another order of addition).  Synchronises.
+
+    rows, intercepts: [score(ctx, F, x, rows=rows, intercept=c) for x, c in zip(xs, intercepts)] from one pass over the rows the list
+    names (Context.margin_stats_multi(rows=, offsets=)); the score's n is the length of the list."""
     from . import _lib as L
     from .host_route import _score
     kind = "logistic" if F.loss == L.LOSS_LOGISTIC else "ls"
-    return [_score(kind, tuple(st), F.N) for st in ctx.margin_stats_multi(F, xs)]
+    n = F.N if rows is None else int(rows.shape[0])
+    return [_score(kind, tuple(st), n) for st in ctx.margin_stats_multi(F, xs, rows=rows, offsets=intercepts)]
 
 
 def best(scores):

@@ -233,6 +233,21 @@ CIAO_API int32_t ciao_margin_stats(ciao_ctx *ctx, const ciao_problem *p, const v
  * or NaN, N = 0, CIAO_LOSS_ZERO and complex problems.  On a row-sharded context: the LOCAL rows, as ciao_row_dots.  Synchronises. */
 CIAO_API int32_t ciao_margin_stats_multi(ciao_ctx *ctx, const ciao_problem *p, int32_t K, const void *const *x,
                                          const double *s_host, double *out_host);
+/* ciao_margin_stats_multi over a LIST of rows, with an offset per model: held-out rows of a fold scored for K
+ * fitted models that each carry an intercept, in one pass over the rows named and without a gathered copy.
+ * idx: M device int64 row numbers in [0, N), 8-byte aligned, any order, repeats allowed; or NULL: every row in order (M must be N).
+ * offset_host: K host doubles, finite, or NULL; model k's per-sample terms see (double)(a_i'x_k) + offset_k, one double addition.
+ * With NULL no addition is made.  s_host, out_host, x: as ciao_margin_stats_multi.
+ * The call over idx gives BIT FOR BIT what the call with idx = NULL gives on the gathered copy A[idx], b[idx], for every ld, base and
+ * alignment of A; with idx = NULL and offset_host = NULL it gives ciao_margin_stats_multi's bits.  A model's bits do not depend on K, on
+ * its place in the list of models or on its neighbours.  An entry of idx outside [0, N) is a row that does not exist: no load is
+ * issued for it and its samples are SKIPPED (not counted as zeros).  Columns [d, ld) and rows the list does not name are never read.
+ * There is no in-call fallback here and the option "mscore_off" does not apply: refused with CIAO_ERR_ARG and nothing launched are
+ * ciao_margin_stats_multi's cases and M < 1, idx not 8-byte aligned, a non-finite offset, idx = NULL with M != N, d > 1024 and an
+ * x[k] that is not 16-byte aligned (score such a model with ciao_list_dots).  ciao_ctx_last_kernel: mscore_partial_kernel<rows,...>.
+ * Synchronises. */
+CIAO_API int32_t ciao_margin_stats_multi_rows(ciao_ctx *ctx, const ciao_problem *p, const int64_t *idx, int64_t M, int32_t K,
+                                              const void *const *x, const double *offset_host, const double *s_host, double *out_host);
 /* ciao_certificate with its per-sample terms.  out_host[0..5] are exactly ciao_certificate's six numbers (av = NULL: the call makes
  * its pass), [6..9] the four numbers of ciao_margin_stats on that pass's row dots with s = min(1, mu / ||grad f(x)||_inf) formed on
  * the device (mu = g->lam for CIAO_PROX_L1 with lam > 0; s = 1 otherwise, and where grad f(x) = 0).  For logistic rows and NormL1
