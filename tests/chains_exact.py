@@ -142,9 +142,10 @@ def live_steps(nsteps, depth, marks, counts=()):
     return sorted(k for k in s if 0 <= k < nsteps)
 
 
-def place_repeats(idx, live, marks, distances, rows, inside_at):
+def place_repeats(idx, live, marks, distances, rows, inside_at, chunks=(CHUNK, WS_RR)):
     """the same (live) row at steps (a, a + k) for every k of `distances`: once with a < m <= a + k for a mark m (the first mark with
-    room), once inside a chunk from `inside_at` on.  Marks idx and live in place -> {k: [(a, a + k, straddled mark or None), ...]}"""
+    room), once inside a chunk from `inside_at` on (`chunks`: the staging lengths no such pair may straddle).  Marks idx and live in place
+    -> {k: [(a, a + k, straddled mark or None), ...]}"""
     used, out, take = set(), {}, rows.pop
     for k in distances:
         out[k] = []
@@ -160,7 +161,7 @@ def place_repeats(idx, live, marks, distances, rows, inside_at):
         a = inside_at
         while a in used or a + k in used:
             a += 1
-        if a + k < len(idx) and all((a - 1) // c == (a + k) // c for c in (CHUNK, WS_RR)):
+        if a + k < len(idx) and all((a - 1) // c == (a + k) // c for c in chunks):
             r = take()
             idx[a] = idx[a + k] = r
             live[a] = live[a + k] = True
